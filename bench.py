@@ -9,11 +9,13 @@ W [4096, 11008] is column-sharded by output feature across ranks (rank r owns ro
 r*N/g .. (r+1)*N/g of W, quantised NF4 bs=64 with nested statistics, the Linear4bit
 default); X [4096, 11008] bf16 is replicated.  Total work is fixed -> "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (driver contract).  Extra fields: int8 igemmlt TOPS
-(metric shape and config 3 = 4096^3), the decode GEMV (config 2) GB/s, the config-1
-dequantize GB/s, the roofline of the dominant kernel and the CPU baseline.
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the --steps steps, writes
+the last step's output when --dump-outputs DIR is given, and prints the line (value, ms_per_step, the roofline of
+the dominant kernel from the timed steps' own stage events).  --full adds everything else after the timed steps:
+the output verification, int8 igemmlt TOPS (metric shape and config 3 = 4096^3), the decode GEMV (config 2) GB/s,
+the config-1 dequantize GB/s, the config 4 / 5 legs, the measured peaks and the CPU baseline.
 
-Launch:  python bench.py [--gpus 1 --steps 20 --warmup 5]
+Launch:  python bench.py [--gpus 1 --steps 20 --warmup 5] [--full] [--dump-outputs DIR]
          python bench.py --gpus N        (N > 1, no launcher: starts N rank processes itself, see launch_ranks)
          python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
@@ -1074,16 +1076,37 @@ def load_pmc_traffic():
     return None
 
 
+DUMP_ROWS = 2048       # token rows of the [M, N] output written by --dump-outputs (32 MiB as float32)
+
+
+def dump_outputs(out_dir, y) -> None:
+    """--dump-outputs DIR: what the last timed step handed its caller, the layer's [M, N] bf16 output (world 1: Y; N > 1:
+    the assembled output on rank 0), as DIR/y.npy in float32 (exact for bf16).  A fixed sample of DUMP_ROWS token rows
+    (seeded permutation, ascending; all N columns of each) keeps the file under 64 MB; the inputs are seeded, so two
+    builds run with the same arguments write the same rows of the same product."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = torch.randperm(y.shape[0], generator=torch.Generator().manual_seed(11))[:DUMP_ROWS].sort().values
+    np.save(os.path.join(out_dir, "y.npy"), y.index_select(0, rows.to(y.device)).float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)   # BASELINE.md: >= 100 launches after 10 warm-up
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-extras", action="store_true", help="skip int8/decode/config-1/cpu legs")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-int8", action="store_true", help="skip the sharded int8 leg")
-    ap.add_argument("--no-decode", action="store_true", help="skip the sharded decode (M = 1) leg")
-    ap.add_argument("--no-ipc", action="store_true", help="N > 1: skip the one-shot peer-memory decode all-gather leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the output verification, "
+                         "the int8 / decode / config legs, the measured peaks and the CPU baseline (a plain run sets up, "
+                         "warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip int8/decode/config-1/cpu legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-int8", action="store_true", help="--full: skip the sharded int8 leg")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the sharded decode (M = 1) leg")
+    ap.add_argument("--no-ipc", action="store_true",
+                    help="--full, N > 1: skip the one-shot peer-memory decode all-gather leg")
     ap.add_argument("--prefetch", action="store_true",
                     help="dequantise each step's weight inside the previous step's GEMM (gemm_4bit prefetch=)")
     ap.add_argument("--prewarm-ms", type=float, default=400.0, help="untimed clock-ramp period before warmup")
@@ -1100,6 +1123,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="print the rank layout (every rank over gloo, no GPU work) and exit: checks the N-rank launch")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     PREFETCH[0] = args.prefetch
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1146,8 +1171,8 @@ def main():
     q_full, st_full = F.quantize_4bit(W, blocksize=BS, quant_type="nf4", compress_statistics=True)
     del W
     q, st = shard_quantized_4bit(q_full, st_full, world, rank)
-    # rank 0: the world-1 sample check after the timed region (verify_sharded_output) needs the full weight
-    nf4_check = nf4_world1_sample(X, q_full, st_full, sample_rows(M)) if rank == 0 else None
+    # --full, rank 0: the world-1 sample check after the timed region (verify_sharded_output) needs the full weight
+    nf4_check = nf4_world1_sample(X, q_full, st_full, sample_rows(M)) if rank == 0 and args.full else None
     if world > 1:
         q = q.clone()
         del q_full
@@ -1241,20 +1266,24 @@ def main():
 
     median_step_ms = clock.median_ms()
 
-    # N > 1: the step's own outputs checked (the last timed step's Y and assembled [M, N]), the communicator and the
-    # devices recorded, the all-gather timed alone -- all outside the timed region
-    verification, dinfo, allgather = None, None, None
     torch.cuda.synchronize()
-    verification = verify_sharded_output(Y, full_out if world > 1 else Y, world, rank, dev, sample_fn=nf4_check)
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full_out if world > 1 else Y)
+
+    # --full: the step's own outputs checked (the last timed step's Y and assembled [M, N]); N > 1: the communicator and
+    # the devices recorded, the all-gather timed alone -- all outside the timed region
+    verification, dinfo, allgather = None, None, None
+    if args.full:
+        verification = verify_sharded_output(Y, full_out if world > 1 else Y, world, rank, dev, sample_fn=nf4_check)
+    if world > 1 and args.full:
         dinfo = dist_info(dev)
         allgather = time_allgather(Y[:Mc], gathered[0], chunks, world, dev)
         allgather["backend"] = backend_label()
 
     extras = {}
-    if not args.no_int8:     # every rank: it contains collectives when world > 1
+    if args.full and not args.no_int8:     # every rank: it contains collectives when world > 1
         extras["int8_igemmlt_sharded"] = bench_int8_sharded(dev, world, rank, args.steps, args.warmup, chunks)
-    if not args.no_decode:   # every rank: the sharded decode step (GEMV + all-gather) as one HIP graph
+    if args.full and not args.no_decode:   # every rank: the sharded decode step (GEMV + all-gather) as one HIP graph
         extras["decode_sharded_config2"] = bench_decode_sharded(dev, world, rank, args.steps, args.warmup)
         row_rccl = extras["decode_sharded_config2"].pop("_row")
         if world > 1 and not args.no_ipc:
@@ -1272,7 +1301,7 @@ def main():
                 extras["decode_sharded_config2_ipc"] = r_ipc
             except Exception as ex:  # noqa: BLE001
                 extras["decode_sharded_config2_ipc"] = {"error": repr(ex)}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras["int8_igemmlt_metric_shape"] = bench_int8(dev, M, N, K)
         extras["int8_igemmlt_config3"] = bench_int8(dev, 4096, 4096, 4096)
         extras["decode_gemv_config2"] = bench_decode_gemv(dev)
@@ -1283,20 +1312,20 @@ def main():
         extras["llama2_7b_prefill_config4"] = bench_llama2_7b_prefill(dev)
         extras["llama2_70b_rank_shard_config5"] = bench_llama2_70b_shard(dev)
     peaks = None
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         try:
             peaks = measure_peaks(dev)
         except Exception as ex:  # noqa: BLE001
             peaks = {"error": str(ex)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not args.no_extras:
         try:
             cpu = cpu_baseline()
         except Exception as ex:  # noqa: BLE001
             cpu = {"value": None, "unit": "TFLOP/s", "cores": None, "kind": "port", "sample": f"failed: {ex}"}
 
     # every rank holds the same combined verdicts (verify_sharded_output all-reduces them)
-    legs = {"nf4_step": verification}
+    legs = {"nf4_step": verification} if args.full else {}
     if world > 1:
         for key in ("int8_igemmlt_sharded", "decode_sharded_config2"):
             if key in extras:
@@ -1350,11 +1379,13 @@ def main():
             "measured_peaks": peaks,
             "cpu_baseline": cpu,
         }
-        line["verification"] = verification
-        if world > 1:
-            line["distributed"] = dinfo
-            line["allgather"] = allgather
-        line["outputs_verified"] = not bad_legs
+        line["full"] = args.full
+        if args.full:
+            line["verification"] = verification
+            if world > 1:
+                line["distributed"] = dinfo
+                line["allgather"] = allgather
+            line["outputs_verified"] = not bad_legs
         if bad_legs:
             line["verification_failed"] = bad_legs
         line.update(extras)

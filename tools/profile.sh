@@ -8,7 +8,7 @@ mkdir -p $OUT profiles
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 # the metric step alone (its kernel means must agree with the bench's event times), then the extra legs
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-extras > $OUT/bench_traced.json 2> $OUT/trace.err || exit 1
-timeout -k 10 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace_extras -- python3 bench.py --steps 2 --warmup 1 --no-cpu > $OUT/bench_traced_extras.json 2> $OUT/trace_extras.err || exit 5
+timeout -k 10 600 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/trace_extras -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu > $OUT/bench_traced_extras.json 2> $OUT/trace_extras.err || exit 5
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d $OUT/fetch -- python3 bench.py --no-extras --no-cpu --steps 3 --warmup 1 > /dev/null 2> $OUT/fetch.err || exit 2
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -T --output-format csv -d $OUT/write -- python3 bench.py --no-extras --no-cpu --steps 3 --warmup 1 > /dev/null 2> $OUT/write.err || exit 3
 # MFMA utilisation and the clock held under load (counters only; durations come from the trace pass above)
