@@ -9,18 +9,14 @@
 // is 16 ds_read_b128 per 64 MFMAs -- a third fewer LDS bytes per MFMA than the 8-wave 128 x 64 split
 // (MI355X_MICROARCH.md 'DVFS give-back': LDS read bytes cost clock).
 //
-// Pipeline (round 4 default, V & 8192: see tile3 below -- three barriers per k-tile, each operand's DMA issued as soon
-// as its rows of the stage are free; the two-half form described next is the round-3 schedule, kept as an A/B arm):
-// two LDS stages of 64 KiB (A and B tiles [256][64], 16-B slots XOR-swizzled by (row >> 1) & 7 through
-// the DMA source address, conflict-free for the fragment reads).  Both operands move by LDS-DMA
-// (global_load_lds_dwordx4, scalar base + one 32-bit lane offset per piece, so ragged edges are clamped once in
-// the offsets and a k-step advances only the scalar base).  Per k-tile t, two halves:
-//   half 1: the 64 MFMAs of k32 step 0 (fragments already in registers) while this wave reads step 1's fragments;
-//           lgkmcnt(0) + barrier: every wave is done with stage t & 1;
-//   half 2: DMA of tile t+2 into that stage, interleaved with step 1's MFMAs; vmcnt(16) (tile t+1 landed) +
-//           barrier; tile t+1's step-0 fragments read under the remaining MFMAs.
-// The DMA of a tile is therefore in flight for a whole k-tile (~2k MFMA cycles), and no vmcnt(0) drain sits in
-// the loop (cdna_hip_programming.md §5 'Pipelining across barriers').
+// Pipeline: two LDS stages of 64 KiB (A and B tiles [256][64], 16-B slots XOR-swizzled by (row >> 1) & 7 through the
+// DMA source address, conflict-free for the fragment reads).  Both operands move by LDS-DMA (global_load_lds_dwordx4,
+// scalar base + one 32-bit lane offset per piece, so ragged edges are clamped once in the offsets and a k-step advances
+// only the scalar base).  One schedule runs: per k-tile t, the MFMAs of k32 step 0 then of step 1 with three barriers
+// between them, one per event "these rows of stage t & 1 are free" (B rows, then A rows) and "tile t+1 has landed", so
+// that tile t+2's pieces are issued as soon as their rows are free and most of them stay in flight across the tile
+// boundary; no vmcnt(0) drain sits in the loop (cdna_hip_programming.md §5 'Pipelining across barriers').  The MFMA
+// positions of every event are in the comment on tile3 in k_hgemm and, per tile shape, in HgPlan3.
 #include "gemm_common.hpp"
 #include "int8_common.hpp"
 
@@ -30,25 +26,9 @@
 
 namespace bnb {
 
-constexpr int HG_BM = 256, HG_BN = 256, HG_BK = 64, HG_THREADS = 256;
-constexpr int HG_TILE = HG_BM * HG_BK * 2;        // 32 KiB per operand per stage
-constexpr int HG_STAGE = 2 * HG_TILE;             // A + B
-constexpr int HG_LDS_MAIN = 2 * HG_STAGE;         // 128 KiB
-// epilogue staging of 16-bit outputs: per wave 128 rows x 256 B, rows padded to 272 B (16-B aligned; the 8-B
-// fragment writes of 16 consecutive rows then hit 2 banks each, 2-way at most)
-constexpr int HG_EPI_PITCH = 272;
-constexpr int HG_LDS_EPI = 4 * 128 * HG_EPI_PITCH;   // 136 KiB
-[[maybe_unused]] constexpr int HG_LDS = HG_LDS_MAIN > HG_LDS_EPI ? HG_LDS_MAIN : HG_LDS_EPI;
-
-// LDS-DMA with a scalar base: lane address = sbase + voff (unsigned 32-bit), 16 B per lane to lds + 16 * lane.
-// M0 (the LDS destination) is written and restored inside the statement (it is compiler-reserved).
-__device__ __forceinline__ void glds16_sv(const void* sbase, uint32_t voff, uint32_t lds) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds)
-               : "memory");
-}
+// (the full tile; LDS per tile shape -- two stages of A + B, or the 16-bit epilogue's staging rows, 256 B padded to
+// 272 B so that the 8-B fragment writes of 16 consecutive rows hit 2 banks each -- is computed in k_hgemm)
+constexpr int HG_BM = 256, HG_BN = 256, HG_THREADS = 256;
 
 typedef float hg_f32x2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 hg_bf16x2_t __attribute__((ext_vector_type(2)));
@@ -73,8 +53,8 @@ template <> __device__ __forceinline__ uint32_t cvt_pk<fp16_t>(float lo, float h
 //   HG_BF16, HG_FP16   v_mfma_f32_16x16x32_{bf16,f16}, fp32 accumulators, one RNE rounding to T at the end
 //   HG_I8_DEQ          v_mfma_i32_16x16x64_i8, exact int32, the fused mm_dequant epilogue to fp16
 //                      (igemmlt + dequant_mm_int32_fp16, ref:sycl/sycl_code/kernel_quant.cpp:3969 order)
-//   HG_I8_I32          the same product stored as int32 (igemmlt's row-major int32 C)
-enum HgOp { HG_BF16 = 0, HG_FP16 = 1, HG_I8_DEQ = 2, HG_I8_I32 = 3 };
+// (the same product stored as int32 is not built here: its epilogue spilled, see igemm_4wave)
+enum HgOp { HG_BF16 = 0, HG_FP16 = 1, HG_I8_DEQ = 2 };
 typedef unsigned hg_u32x4_t __attribute__((ext_vector_type(4)));
 typedef int hg_i32x4_t __attribute__((ext_vector_type(4)));
 template <int OP> struct HgOpT;
@@ -104,7 +84,7 @@ template <> struct HgOpT<HG_FP16> {
     return c;
   }
 };
-struct HgOpI8 {
+template <> struct HgOpT<HG_I8_DEQ> {
   typedef hg_i32x4_t acc_t;
   static constexpr int ELEM = 1;
   __device__ static __forceinline__ acc_t mma(const hg_u32x4_t& a, const hg_u32x4_t& b, acc_t c) {
@@ -117,12 +97,11 @@ struct HgOpI8 {
     return c;
   }
 };
-template <> struct HgOpT<HG_I8_DEQ> : HgOpI8 {};
-template <> struct HgOpT<HG_I8_I32> : HgOpI8 {};
 
-// The same without saving / restoring M0: valid only in a kernel whose code uses M0 for nothing else (k_hgemm: no
-// LDS-DMA builtin, no s_sendmsg / movrel / LDS-parameter access -- `grep m0` of its .s shows only these statements).
-// The s_nop 0 is the M0-write -> LDS-DMA wait state.
+// LDS-DMA with a scalar base: lane address = sbase + voff (unsigned 32-bit), 16 B per lane to lds + 16 * lane.  M0 (the
+// LDS destination, compiler-reserved) is written and not restored: valid only in a kernel whose code uses M0 for nothing
+// else (k_hgemm: no LDS-DMA builtin, no s_sendmsg / movrel / LDS-parameter access -- `grep m0` of its .s shows only
+// these statements; tests/test_kernel_resources.py checks it).  The s_nop 0 is the M0-write -> LDS-DMA wait state.
 __device__ __forceinline__ void glds16_sv_m0(const void* sbase, uint32_t voff, uint32_t lds) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds) : "memory");
 }
@@ -134,34 +113,6 @@ __device__ __forceinline__ void glds16_chain(const void* sbase, uint32_t voff) {
   asm volatile("global_load_lds_dwordx4 %0, %1\n\ts_add_u32 m0, m0, %2" : : "v"(voff), "s"(sbase), "i"(STEP) : "memory");
 }
 __device__ __forceinline__ void hg_set_m0(uint32_t lds) { asm volatile("s_mov_b32 m0, %0" : : "s"(lds) : "memory"); }
-
-// HG_DMA_BUF (round-6 A/B build switch): the LDS-DMA pieces as MUBUF `buffer_load_dwordx4 ... offen lds` (a buffer
-// resource over the operand, the k-tile's byte offset in soffset, the same per-piece VGPR offsets) instead of the
-// FLAT-encoded `global_load_lds_dwordx4`.  Same bytes to the same LDS slots, bit-identical outputs -- and 2.5-3.4 %
-// slower (metric shape 230.0 -> 237.1 us, 4096^3 90.4 -> 93.5, int8 121.9 -> 124.9; tools/r06_hg_variant.sh,
-// profiles/lab/r06_hg_dma_buf_ab.json), so the library keeps the FLAT form (0).
-#ifndef HG_DMA_BUF
-#define HG_DMA_BUF 0
-#endif
-typedef int hg_rsrc_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ hg_rsrc_t hg_rsrc(const void* base) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  // dword1: base[47:32], stride 0; dword2: num_records (no range check in practice: the offsets stay < 4 GiB);
-  // dword3: the raw-buffer word of common.hpp's loads (DATA_FORMAT 32)
-  hg_rsrc_t r = {(int)(uint32_t)a, (int)((uint32_t)(a >> 32) & 0xFFFFu), -1, 0x00020000};
-  r[0] = __builtin_amdgcn_readfirstlane(r[0]);
-  r[1] = __builtin_amdgcn_readfirstlane(r[1]);
-  return r;
-}
-template <int STEP>
-__device__ __forceinline__ void glds16_chain_buf(hg_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2 offen lds\n\ts_add_u32 m0, m0, %3" : : "v"(voff), "s"(rsrc), "s"(soff), "i"(STEP)
-               : "memory");
-}
-__device__ __forceinline__ void glds16_buf_m0(hg_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds) {
-  asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds)
-               : "memory");
-}
 
 __device__ __forceinline__ int hg_swz(int r, int s) { return r * 128 + ((s ^ ((r >> 1) & 7)) << 4); }
 
@@ -185,20 +136,9 @@ __device__ __forceinline__ uint32_t mm_dequant_pair(int32_t a0, int32_t a1, floa
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, hg_f16x2_t));
 }
 
-// V: schedule variant bits (A/B arms of tools/hgemm_lab.hip; HG_V is the launched one):
-//   1 = step-1 fragment reads all after half 1's MFMAs, 2 = no sched_barrier fences in half 2,
-//   4 = next-step fragments read in MFMA-need order, 8 = DMA spread (8 pieces before the wait, 8 after, one per
-//   4 MFMAs; 1.6 PFLOP/s vs 1.44 for 0 at 4096 x 4096 x 11008, profiles/lab/r03_hgemm_variants.txt), 16 = LDS-DMA
-//   without the M0 save / restore (another 2-3 %, profiles/lab/r03_hgemm_dma_variants.txt), 32 = 12 pieces before
-//   the wait (no gain), 4096 = M0 chained from piece to piece (one s_add per piece instead of s_add + s_mov + s_nop:
-//   another 2-3 %, profiles/lab/r03_hgemm_m0_chain.txt).  Lab-only ablations (wrong results, timing only): 64 = no
-//   vmcnt wait, 128 / 256 = no barrier B2 / B1, 512 = register-staged copies (slower: 256 vs 242 us), 1024 = no
-//   copies, 2048 = no fragment re-reads (profiles/lab/r03_hgemm_ablation.txt).  Launched: 8 + 16 + 4096.
-// Round 4: the three-barrier operand-split schedule (V & 8192, tile3 below) is the launched one: bit-identical to the
-// two-half schedule and 0.8-1.5 % faster at 4096 x 4096 x 11008 (bf16 234.6-235.3 vs 236.6-238.6 us; int8 4-wave
-// 127.3-129.3 vs 128.7-129.3 us; tools/hgemm_variant_ab.py, profiles/lab/r04_hgemm_variants.txt).  The round-3
-// two-half schedule is no longer launched (round 6): its compiled loop carried accumulator copies between the asm MFMAs
-// (the note "The round-3 two-half schedule ..." below); the code stays for tools/hgemm_lab.hip.
+// V: the schedule / feature bits of a k_hgemm instantiation.  HG_V is in every one; its low bits once chose between
+// schedule arms that are gone (the round-3 two-half schedule, the M0 save / restore DMA form) and now select nothing --
+// the value stays so that the kernels keep their names (tests/test_kernel_resources.py, profiles/).
 constexpr int HG_V = 16 + 8192;
 // variant bit: the full-tile 16-bit epilogue stores C write-through (sc1), so the launch ends with no dirty L2 lines for
 // the next kernel's boundary to write back (chgemm_set_c_store; on by default: int8 igemmlt+dequant at the metric shape
@@ -227,24 +167,12 @@ __device__ __forceinline__ unsigned long long hg_now() {
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
   return t;
 }
-// The round-3 two-half schedule (V = 8 + 16 + 4096) was the run-time A/B arm chgemm_set_variant(1) until round 6, when
-// the cause of its int8 non-determinism (round 5, profiles/lab/r05_diag_int8_variant.txt) was found in the ISA, not in
-// the waits: hipcc's register allocator, which sees an asm MFMA as an opaque statement, rotated accumulators through the
-// two-half loop with v_accvgpr_read / v_accvgpr_mov (192-208 of them between the MFMAs of the V = 4120 kernels, e.g.
-// `v_accvgpr_read_b32 v167, a55` six MFMAs after the asm MFMA that writes a[52:55]), without the MFMA -> AGPR-read wait
-// states that its hazard recognizer inserts only for MFMAs it knows -- so a copy could read an accumulator before the
-// MFMA wrote it, and which value it read depended on timing (only element 0 of acc[3][*] in the int8 kernel: one copied
-// register of the rotation).  The bf16 / fp16 arms carried the same copies and passed by timing alone.  The arm is
-// gone; tests/test_kernel_resources.py now checks that no k_hgemm kernel has an accumulator read, write or move between
-// its first and last MFMA.
-// lda / ldb / ldc in elements of the operand / output type.  rowStats / colStats / bias: HG_I8_DEQ only.
-// SPLIT (bf16 / fp16 only): the split-K form -- its epilogue stores fp32 partials only.  A separate instantiation, so
-// that each kernel has ONE epilogue reading the accumulators (two in one kernel made the allocator spill).
-// Compile-time positions of the three-barrier schedule per tile shape (MFMA index q of the k-tile after which each
-// event is issued; -1 = none).  256 x 256 (8, 8): 128 MFMAs, 16 pieces, vmcnt(13) at B3.  256 x 128 (8, 4) and
-// 128 x 256 (4, 8): 64 MFMAs, 12 pieces -- the same order scaled: the stage's B rows are read first (w1), then B1; the
-// B pieces go in while x1 is read; B2; the A pieces; B3 with the pieces issued so far left in flight; the next
-// tile's step-0 fragments one per 2 MFMAs to the end, beside the last A pieces.
+// The asm MFMAs are opaque to hipcc's register allocator and hazard recognizer: a schedule whose compiled loop rotates
+// accumulators (v_accvgpr_read / mov between the MFMAs) reads them without the MFMA -> AGPR-read wait states, and
+// which value it reads depends on timing (the round-3 two-half schedule did, profiles/lab/r05_diag_int8_variant.txt;
+// removed).  tests/test_kernel_resources.py checks that no k_hgemm kernel has an accumulator read, write or move
+// between its first and last MFMA.
+
 // compile-time loop: f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>)
 template <class F, int... Q>
 __device__ __forceinline__ void hg_static_for_impl(F&& f, std::integer_sequence<int, Q...>) {
@@ -255,43 +183,21 @@ __device__ __forceinline__ void hg_static_for(F&& f) {
   hg_static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// Compile-time positions of the three-barrier schedule per tile shape (MFMA index q of the k-tile after which each
+// event is issued; -1 = none).  256 x 256 (8, 8): 128 MFMAs, 16 pieces, vmcnt(13) at B3.  256 x 128 (8, 4) and
+// 128 x 256 (4, 8): 64 MFMAs, 12 pieces -- the same order scaled: the stage's B rows are read first (w1), then B1; the
+// B pieces go in while x1 is read; B2; the A pieces; B3 with the pieces issued so far left in flight; the next
+// tile's step-0 fragments one per 2 MFMAs to the end, beside the last A pieces.
 template <int WI, int WJ> struct HgPlan3;
-// (lab: tools/hgemm_plan_sweep.sh builds the lab with these positions moved -- HG_P3_DB1 / DB2 / DB3 shift barrier B1 /
-// B2 / B3 and everything keyed to it; the library is built with all three 0)
-#ifndef HG_P3_DB1
-#define HG_P3_DB1 0
-#endif
-#ifndef HG_P3_DB2
-#define HG_P3_DB2 0
-#endif
-#ifndef HG_P3_DB3
-#define HG_P3_DB3 0
-#endif
-#ifndef HG_P3_ABL
-#define HG_P3_ABL 0
-#endif
-#ifndef HG_P3_AEARLY
-#define HG_P3_AEARLY 0
-#endif
-template <> struct HgPlan3<8, 8> {
-  static constexpr int D1 = HG_P3_DB1, D2 = HG_P3_DB2, D3 = HG_P3_DB3;
-  // HG_P3_AEARLY (lab): the last 3 A pieces before B3 too (q B2 + 32, 34, 36), so B3 waits vmcnt(16) and the next
-  // tile's fragment-read burst carries no DMA
-  static constexpr int AE = HG_P3_AEARLY;
-  static constexpr int B1 = 21 + D1, B2 = 50 + D2, B3 = 88 + D3, SETB = 22 + D1, SETA = 61 + D2, VM = AE ? 16 : 13,
-                       SIDEQ = 120;
+template <> struct HgPlan3<8, 8> {                      // 256 x 256: 8 B pieces, 8 A pieces per wave
+  static constexpr int B1 = 21, B2 = 50, B3 = 88, SETB = 22, SETA = 61, VM = 13, SIDEQ = 120;
   __host__ __device__ static constexpr int wread(int q) { return q < 16 && (q & 1) == 0 ? q >> 1 : -1; }
-  __host__ __device__ static constexpr int xread(int q) {
-    return q >= 23 + D1 && q <= 44 + D1 && (q - 23 - D1) % 3 == 0 ? (q - 23 - D1) / 3 : -1;
-  }
+  __host__ __device__ static constexpr int xread(int q) { return q >= 23 && q <= 44 && (q - 23) % 3 == 0 ? (q - 23) / 3 : -1; }
   __host__ __device__ static constexpr int bpiece(int q) {
-    return q == 24 + D1 ? 0 : q == 28 + D1 ? 1 : q == 32 + D1 ? 2 : q == 36 + D1 ? 3 : q == 40 + D1 ? 4
-         : q == 52 + D2 ? 5 : q == 56 + D2 ? 6 : q == 60 + D2 ? 7 : -1;
+    return q == 24 ? 0 : q == 28 ? 1 : q == 32 ? 2 : q == 36 ? 3 : q == 40 ? 4 : q == 52 ? 5 : q == 56 ? 6 : q == 60 ? 7 : -1;
   }
   __host__ __device__ static constexpr int apiece(int q) {
-    return q == 64 + D2 ? 0 : q == 68 + D2 ? 1 : q == 72 + D2 ? 2 : q == 76 + D2 ? 3 : q == 80 + D2 ? 4
-         : AE ? (q == 82 + D2 ? 5 : q == 84 + D2 ? 6 : q == 86 + D2 ? 7 : -1)
-              : (q == 97 + D3 ? 5 : q == 107 + D3 ? 6 : q == 117 + D3 ? 7 : -1);
+    return q == 64 ? 0 : q == 68 ? 1 : q == 72 ? 2 : q == 76 ? 3 : q == 80 ? 4 : q == 97 ? 5 : q == 107 ? 6 : q == 117 ? 7 : -1;
   }
   __host__ __device__ static constexpr int nread(int q) { return q > B3 && q <= B3 + 31 && ((q - B3 - 1) & 1) == 0 ? (q - B3 - 1) >> 1 : -1; }
 };
@@ -349,10 +255,10 @@ struct HgSide {
   void* out;                 // ndw * 8 outputs of the GEMM's type (16-B aligned)
   long long ndw;             // packed dwords (elements / 8)
   int per_wg, iters, every, bs_shift, bs2_shift, nested, fp4;
-  int mode;                  // A/B bits (chgemm_set_side_mode): 1 = non-temporal packed loads / output stores; 128 =
-                             // the round-4 in-loop form instead of the tail form (below); lab ablations (timing only,
-                             // wrong weights): 2 = no side stores, 8 = no consumption, 16 = no side loads, 32 = no side
-                             // step in the loop, 64 = no tail
+  int mode;                  // A/B bits (chgemm_set_side_mode): 128 = the round-4 in-loop form instead of the tail form
+                             // (below); read by the in-loop form only: 1 = non-temporal packed loads / output stores,
+                             // and the lab ablations (timing only, wrong weights) 2 = no side stores, 8 = no
+                             // consumption, 16 = no side loads, 32 = no side step in the loop, 64 = no tail
 };
 static Knob<int> g_side_mode{1};
 
@@ -417,8 +323,8 @@ __device__ __forceinline__ void hg_tail_store(const HgSide& side, const float2* 
 // The tail form's loop, run by every wave on its own after the epilogue: no workgroup barrier (a barrier's release
 // fence would wait for every store issued so far), the wave's own LDS copy of the code-pair table (2 KiB) and nested
 // code map (1 KiB) in its own epilogue staging rows (`ep`, which it has finished reading: LDS operations of one wave
-// run in order), its first chunk by its wave index and the rest from the counter, and each chunk's loads issued before
-// the previous chunk is converted and stored (two register sets).
+// run in order), chunk c going to wave c mod waves (a static assignment, no counter), and each chunk's loads issued
+// before the previous chunk is converted and stored (two register sets).
 template <typename T16>
 __device__ __forceinline__ void hg_side_tail(const HgSide& side, uint8_t* ep, int lane, uint32_t wave_id,
                                              uint32_t waves) {
@@ -456,6 +362,9 @@ __device__ __forceinline__ void hg_side_tail(const HgSide& side, uint8_t* ep, in
   }
 }
 
+// lda / ldb / ldc in elements of the operand / output type.  rowStats / colStats / bias: HG_I8_DEQ only.
+// SPLIT (bf16 / fp16 only): the split-K form -- its epilogue stores fp32 partials only.  A separate instantiation, so
+// that each kernel has ONE epilogue reading the accumulators (two in one kernel made the allocator spill).
 template <int OP, int V = 0, bool SPLIT = false, int WI = 8, int WJ = 8, bool SIDE = false>
 __global__ void __launch_bounds__(HG_THREADS, 1)
 k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const void* __restrict__ Bv, long long ldb,
@@ -464,9 +373,10 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   using Op = HgOpT<OP>;
   using acc_t = typename Op::acc_t;
   constexpr int E = Op::ELEM;
-  static_assert(!SIDE || ((OP == HG_BF16 || OP == HG_FP16) && (V & 8192) != 0), "side dequantise: 16-bit, tile3");
-  // tile shape: 2 x 2 waves of (16 WI) x (16 WJ) outputs -- 256 x 256 (8, 8), 256 x 128 (8, 4), 128 x 256 (4, 8)
-  static_assert((WI == 8 && WJ == 8) || (V & 8192) != 0, "tile shapes other than 256 x 256 run the three-barrier schedule");
+  static_assert((V & HG_V) == HG_V, "V = HG_V plus feature bits");
+  static_assert(!SIDE || OP == HG_BF16 || OP == HG_FP16, "side dequantise: 16-bit kinds");
+  // tile shape: 2 x 2 waves of (16 WI) x (16 WJ) outputs -- 256 x 256 (8, 8), 256 x 128 (8, 4), 128 x 256 (4, 8),
+  // 128 x 128 (4, 4)
   constexpr int BM = 32 * WI, BN = 32 * WJ;
   constexpr int TA = BM * 128, STG = TA + BN * 128;     // A tile, then B tile, per stage
   constexpr int EPI_PITCH = 32 * WJ + 16;               // 16-bit output staging row per wave (16 B of padding)
@@ -618,17 +528,8 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   }
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)smem);
   const uint32_t ldsA0 = lds_base + wave * WI * 1024, ldsB0 = lds_base + TA + wave * WJ * 1024;
-  [[maybe_unused]] const hg_rsrc_t rsA = hg_rsrc(A), rsB = hg_rsrc(B);
-  auto dma_a = [&](int kt, int st, int i) {
-    if constexpr (HG_DMA_BUF && (V & 16) != 0) glds16_buf_m0(rsA, aoff[i], (uint32_t)kt * 128u, ldsA0 + st * STG + i * 1024);
-    else if constexpr ((V & 16) != 0) glds16_sv_m0(A + (long long)kt * 128, aoff[i], ldsA0 + st * STG + i * 1024);
-    else glds16_sv(A + (long long)kt * 128, aoff[i], ldsA0 + st * STG + i * 1024);
-  };
-  auto dma_b = [&](int kt, int st, int i) {
-    if constexpr (HG_DMA_BUF && (V & 16) != 0) glds16_buf_m0(rsB, boff[i], (uint32_t)kt * 128u, ldsB0 + st * STG + i * 1024);
-    else if constexpr ((V & 16) != 0) glds16_sv_m0(B + (long long)kt * 128, boff[i], ldsB0 + st * STG + i * 1024);
-    else glds16_sv(B + (long long)kt * 128, boff[i], ldsB0 + st * STG + i * 1024);
-  };
+  auto dma_a = [&](int kt, int st, int i) { glds16_sv_m0(A + (long long)kt * 128, aoff[i], ldsA0 + st * STG + i * 1024); };
+  auto dma_b = [&](int kt, int st, int i) { glds16_sv_m0(B + (long long)kt * 128, boff[i], ldsB0 + st * STG + i * 1024); };
 
   // ---- fragments: MFMA A operand = B rows (n), MFMA B operand = A rows (m), so D[n][m] and a lane's 4 results
   // are 4 consecutive n of one m: one 8-B store per accumulator.  Row keys ((row >> 1) & 7) do not depend on the
@@ -648,148 +549,7 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   frag_t w0[WJ], x0[WI], w1[WJ], x1[WI];
   const int nk = min(kchunk, K * E / 128 - kt0);   // k-tiles of 128 bytes in this split (>= 1 by the host rule)
 
-  // V & 512 (lab): register-staged copies instead of LDS-DMA -- ordinary 16-B global loads into 16 staging registers
-  // (same swizzled source offsets), written to the same LDS slots one k-tile later by ds_write_b128.  The writes of
-  // tile t+1 finish before half 1's barrier, so that barrier alone orders them against the reads: one barrier per
-  // k-tile, no vmcnt bookkeeping of ours (hipcc counts the ordinary loads).
-  constexpr bool RS = (V & 512) != 0;
-  frag_t sg[RS ? 16 : 1];
-  auto rs_load = [&](int kt, int q) {
-    if constexpr (RS) {
-      const uint8_t* base = (q < 8 ? A : B) + (long long)kt * 128;
-      sg[q] = *reinterpret_cast<const frag_t*>(base + (q < 8 ? aoff[q] : boff[q - 8]));
-    }
-  };
-  auto rs_write = [&](int st, int q) {
-    if constexpr (RS)
-      *reinterpret_cast<frag_t*>(smem + st * STG + (q < 8 ? 0 : TA) + wave * 8192 + (q & 7) * 1024 +
-                                 16 * lane) = sg[q];
-  };
-
-  // half 1 of k-tile t (stage st): the 64 MFMAs of k32 step 0, step 1's fragments of the stage read underneath (one
-  // read per 4 MFMAs); then this wave's reads are retired and the barrier says every wave is done with the stage.
-  // FIRST: tile 0 starts the accumulators (SrcC = 0, so no zero-fill of the AGPRs is needed).
-  auto half1 = [&](auto first, int t) {
-    const int st = t & 1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        if constexpr (decltype(first)::value) acc[j][i] = Op::mma0(w0[j], x0[i]);
-        else acc[j][i] = Op::mma(w0[j], x0[i], acc[j][i]);
-        if constexpr (RS) {
-          // register staging: piece q of tile t+1 into stage st ^ 1, then tile t+2's piece q into the same registers
-          const int q = 2 * j + (i >> 2);
-          if ((i & 3) == 0) rs_write(st ^ 1, q);
-          if ((i & 3) == 1) rs_load(min(t + 2, nk - 1), q);
-        }
-        if (!(V & 1) && !(V & 2048) && (i & 3) == 3) {   // (V & 2048: lab ablation, no fragment re-reads)
-          const int q = 2 * j + (i >> 2);               // 0..15
-          if (q < 8) w1[q] = rd(st, wo1, q);
-          else x1[q - 8] = rd(st, xo1, q - 8);
-        }
-      }
-      if (!(V & 1)) __builtin_amdgcn_sched_barrier(0);
-    }
-    if (V & 1) {
-#pragma unroll
-      for (int f = 0; f < 8; ++f) { w1[f] = rd(st, wo1, f); x1[f] = rd(st, xo1, f); }
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // lgkmcnt(0): this wave's reads of stage st are done
-    if constexpr ((V & 256) == 0) __builtin_amdgcn_s_barrier();   // ... and every other wave's (V & 256: lab ablation)
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  // half 2 of k-tile t: the 64 MFMAs of step 1.  Unless LAST: tile t+2's DMA into stage st under the first 32 (one
-  // piece per 2 MFMAs; past the end the last tile is re-loaded into a stage nobody reads again, so the body stays
-  // branch-free), vmcnt(16) = tile t+1 landed for this wave + barrier = for every wave, and tile t+1's step-0
-  // fragments read under the last 32.
-  auto half2 = [&](auto last, int t, int st) {
-    constexpr bool L = decltype(last)::value;
-    // PRE of the 16 DMA pieces go in before the wait for tile t+1, spread over the first 32 MFMAs; the rest after it,
-    // spread over the last 32 (V & 8: 8 / 8; V & 32: 12 / 4; neither: 16 / 0, one per 2 MFMAs)
-    constexpr int PRE = (V & 32) ? 12 : (V & 8) ? 8 : 16;
-    const int kn = min(t + 2, nk - 1);
-    auto dma = [&](int q) {
-      if constexpr ((V & 1024) != 0) return;            // lab ablation: no copies at all (timing only)
-      if constexpr ((V & 4096) != 0) {                   // M0 chained from piece to piece (pieces issued in order)
-        if (q < 7) glds16_chain<1024>(A + (long long)kn * 128, aoff[q]);
-        else if (q == 7) glds16_chain<TA - 7 * 1024>(A + (long long)kn * 128, aoff[7]);
-        else glds16_chain<1024>(B + (long long)kn * 128, boff[q - 8]);
-        return;
-      }
-      if (q < 8) dma_a(kn, st, q);
-      else dma_b(kn, st, q - 8);
-    };
-    if constexpr (!L && (V & 4096) != 0) hg_set_m0(ldsA0 + st * STG);
-    // fragment q of the next step 0, in the order its MFMAs need them (w0[0], x0[0..7], w0[1..7]) unless V & 4 == 0
-    auto rdn = [&](int q) {
-      if constexpr ((V & 4) != 0) {
-        if (q == 0) w0[0] = rd(st ^ 1, wo0, 0);
-        else if (q <= 8) x0[q - 1] = rd(st ^ 1, xo0, q - 1);
-        else w0[q - 8] = rd(st ^ 1, wo0, q - 8);
-      } else {
-        if (q < 8) w0[q] = rd(st ^ 1, wo0, q);
-        else x0[q - 8] = rd(st ^ 1, xo0, q - 8);
-      }
-    };
-    // DMA piece issued after MFMA `mi` (0..31) of a part holding `cnt` pieces: pieces land on MFMAs
-    // (q + 1) * 32 / cnt - 1, q = 0 .. cnt - 1 (evenly spread, the last one on the part's last MFMA)
-    auto piece_at = [](int mi, int cnt) -> int {
-      for (int q = 0; q < cnt; ++q)
-        if (((q + 1) * 32) / cnt - 1 == mi) return q;
-      return -1;
-    };
-    if constexpr (RS) {
-      // register staging: tile t+1 is already in stage st ^ 1 for every wave (half 1's barrier); its step-0
-      // fragments are read under all 64 MFMAs, one per 4
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          acc[j][i] = Op::mma(w1[j], x1[i], acc[j][i]);
-          if constexpr (!L) if ((i & 3) == 3) rdn(2 * j + (i >> 2));
-        }
-        if (!(V & 2)) __builtin_amdgcn_sched_barrier(0);
-      }
-      return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        acc[j][i] = Op::mma(w1[j], x1[i], acc[j][i]);
-        if constexpr (!L) {
-          const int q = piece_at(8 * j + i, PRE);
-          if (q >= 0) dma(q);
-        }
-      }
-      if (!(V & 2)) __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (!L) {
-      // (V & 64 / V & 128: lab ablations that drop the wait / the barrier -- wrong results, timing only)
-      if constexpr ((V & 64) != 0) {
-      } else if constexpr (PRE == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");   // tile t+1 landed (this wave)
-      else if constexpr (PRE == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      if constexpr ((V & 128) == 0) __builtin_amdgcn_s_barrier();      // ... every wave's pieces
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int j = 4; j < 8; ++j) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        acc[j][i] = Op::mma(w1[j], x1[i], acc[j][i]);
-        if constexpr (!L) {
-          if (!(V & 2048) && (i & 1) == 1) rdn(4 * (j - 4) + (i >> 1));       // fragments 0..15
-          const int q = piece_at(8 * (j - 4) + i, 16 - PRE);
-          if (q >= 0) dma(PRE + q);
-        }
-      }
-      if (!(V & 2)) __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-
-  // V & 8192: the operand-split schedule, three barriers per k-tile.  For the 256 x 256 tile (WI = WJ = 8, 128 MFMAs per
+  // The operand-split schedule, three barriers per k-tile.  For the 256 x 256 tile (WI = WJ = 8, 128 MFMAs per
   // k-tile), MFMA index q:
   //   q 0..14   this wave reads step 1's B fragments (w1) of the stage, one per 2 MFMAs;
   //   q 21      lgkmcnt(0) + barrier B1: every wave is done with the stage's B rows, so tile t+2's B pieces go into
@@ -798,9 +558,9 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   //   q 88      vmcnt(13) (the 13 pieces issued so far in this k-tile may still fly: tile t+1, issued one k-tile
   //             earlier, has landed for this wave) + barrier B3 (... for every wave); tile t+1's step-0 fragments are
   //             read under the remaining 39 MFMAs (one per 2), beside the last 3 A pieces.
-  // So a piece is issued as soon as its rows are free (from MFMA 24 instead of 64) and 13 of 16 stay in flight across
-  // the tile boundary; the fragment reads of a k-tile never share an MFMA gap with more than one DMA issue.  The
-  // half-width tiles (64 MFMAs per k-tile, 12 pieces) follow the same order on the HgPlan3 positions below.
+  // So a piece is issued as soon as its rows are free (from MFMA 24 on) and 13 of 16 stay in flight across the tile
+  // boundary; the fragment reads of a k-tile never share an MFMA gap with more than one DMA issue.  The half-width
+  // tiles (64 MFMAs per k-tile, 12 pieces) and the 128 x 128 tile follow the same order on their HgPlan3 positions.
   using P3 = HgPlan3<WI, WJ>;
   int sd_cd = 0;                                          // k-tiles until the next side step
   auto tile3 = [&](auto first, auto last, int t) {
@@ -829,34 +589,21 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
       } else {
         acc[j][i] = Op::mma(w1[j], x1[i], acc[j][i]);
       }
-      // (HG_P3_ABL lab bits, timing only: 16 = no LDS-DMA pieces in the loop, 32 = no fragment reads in the loop)
-      if constexpr ((HG_P3_ABL & 32) == 0) {
-        if constexpr (P3::wread(q) >= 0) w1[P3::wread(q)] = rd(st, wo1, P3::wread(q));
-        if constexpr (P3::xread(q) >= 0) x1[P3::xread(q)] = rd(st, xo1, P3::xread(q));
-      }
+      if constexpr (P3::wread(q) >= 0) w1[P3::wread(q)] = rd(st, wo1, P3::wread(q));
+      if constexpr (P3::xread(q) >= 0) x1[P3::xread(q)] = rd(st, xo1, P3::xread(q));
       if constexpr (q == P3::B1 || q == P3::B2) {
-        // (HG_P3_ABL, lab builds only -- races, wrong results, timing only: 1 = no barrier at B1 / B2, 2 = no wait)
-        if constexpr ((HG_P3_ABL & 2) == 0) __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0)
-        if constexpr (!L && (HG_P3_ABL & 1) == 0) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0)
+        if constexpr (!L) __builtin_amdgcn_s_barrier();
       }
       if constexpr (!L) {
         if constexpr (q == P3::SETB) hg_set_m0(ldsB0 + st * STG);
-        if constexpr (P3::bpiece(q) >= 0 && (HG_P3_ABL & 16) == 0) {
-          if constexpr (HG_DMA_BUF) glds16_chain_buf<1024>(rsB, boff[P3::bpiece(q)], (uint32_t)kn * 128u);
-          else glds16_chain<1024>(B + (long long)kn * 128, boff[P3::bpiece(q)]);
-        }
+        if constexpr (P3::bpiece(q) >= 0) glds16_chain<1024>(B + (long long)kn * 128, boff[P3::bpiece(q)]);
         if constexpr (q == P3::SETA) hg_set_m0(ldsA0 + st * STG);
-        if constexpr (P3::apiece(q) >= 0 && (HG_P3_ABL & 16) == 0) {
-          if constexpr (HG_DMA_BUF) glds16_chain_buf<1024>(rsA, aoff[P3::apiece(q)], (uint32_t)kn * 128u);
-          else glds16_chain<1024>(A + (long long)kn * 128, aoff[P3::apiece(q)]);
-        }
+        if constexpr (P3::apiece(q) >= 0) glds16_chain<1024>(A + (long long)kn * 128, aoff[P3::apiece(q)]);
         if constexpr (q == P3::B3) {
-          // (HG_P3_ABL lab bits: 4 = no vmcnt wait at B3, 8 = no barrier at B3 -- timing only)
-          if constexpr ((HG_P3_ABL & 4) == 0) {
-            if (SIDE && sd_i1 >= 0) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(P3::VM + 3) : "memory");  // (+ its 3 loads)
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(P3::VM) : "memory");
-          }
-          if constexpr ((HG_P3_ABL & 8) == 0) __builtin_amdgcn_s_barrier();
+          if (SIDE && sd_i1 >= 0) asm volatile("s_waitcnt vmcnt(%0)" ::"i"(P3::VM + 3) : "memory");  // (+ its 3 loads)
+          else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(P3::VM) : "memory");
+          __builtin_amdgcn_s_barrier();
           if constexpr (SIDE) if (sd_i2 >= 0 && !(side.mode & 8)) side_words(sd_i2);   // issued two k-tiles ago:
         }                                                                                 // covered by this wait
         if constexpr (SIDE) {                            // (3 MFMAs between the dependent LDS reads and their use)
@@ -875,7 +622,7 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
           }
           if constexpr (q == P3::SIDEQ) if (sd_go && sd_it < side.iters) side_issue();
         }
-        constexpr int r = (HG_P3_ABL & 32) ? -1 : P3::nread(q);   // w0[0], x0[0..WI-1], w0[1..WJ-1]: their use order
+        constexpr int r = P3::nread(q);                  // w0[0], x0[0..WI-1], w0[1..WJ-1]: their use order
         if constexpr (r == 0) w0[0] = rd(st ^ 1, wo0, 0);
         else if constexpr (r > 0 && r <= WI) x0[r - 1] = rd(st ^ 1, xo0, r - 1);
         else if constexpr (r > WI) w0[r - WI] = rd(st ^ 1, wo0, r - WI);
@@ -885,63 +632,44 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   };
 
   // ---- prologue: tiles 0 and 1 in flight, tile 0 landed, its step-0 fragments in registers
-  if constexpr (RS) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) rs_load(0, q);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) rs_write(0, q);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) rs_load(min(1, nk - 1), q);
-    __syncthreads();
-  } else {
-    if constexpr (OP == HG_I8_DEQ) {
-      // the statistics first (older than tile 0's pieces: the prologue's vmcnt below covers them); lanes past the
-      // matrix edge fetch the last row / column (those slots are read only by the edge path, which does not use them)
-      const uint32_t sb = lds_base + LDS_BYTES + SIDE_LDS;
-      for (int c = wave; c < BM / 64; c += 4)
-        glds4_sv_m0(rowStats, 4u * (uint32_t)min(m0 + 64 * c + lane, M - 1), sb + 256 * c);
-      for (int c = wave; c < BN / 64; c += 4)
-        glds4_sv_m0(colStats, 4u * (uint32_t)min(n0 + 64 * c + lane, N - 1), sb + 4 * BM + 256 * c);
-      if (bias != nullptr && (N & 1) == 0)                 // bias as fp16 pairs (whole dwords: N even)
-        for (int c = wave; c < BN / 128; c += 4)
-          glds4_sv_m0(bias, 4u * (uint32_t)min(n0 / 2 + 64 * c + lane, N / 2 - 1), sb + 4 * BM + 4 * BN + 256 * c);
-    }
-#pragma unroll
-    for (int i = 0; i < WI; ++i) dma_a(0, 0, i);
-#pragma unroll
-    for (int i = 0; i < WJ; ++i) dma_b(0, 0, i);
-    const int k1 = min(1, nk - 1);
-#pragma unroll
-    for (int i = 0; i < WI; ++i) dma_a(k1, 1, i);
-#pragma unroll
-    for (int i = 0; i < WJ; ++i) dma_b(k1, 1, i);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(WI + WJ) : "memory");   // tile 0 landed; tile 1 in flight
-    if constexpr (SIDE) __builtin_amdgcn_s_waitcnt(0xC07F);          // (the side tables' LDS writes)
-    __builtin_amdgcn_s_barrier();
+  if constexpr (OP == HG_I8_DEQ) {
+    // the statistics first (older than tile 0's pieces: the prologue's vmcnt below covers them); lanes past the
+    // matrix edge fetch the last row / column (those slots are read only by the edge path, which does not use them)
+    const uint32_t sb = lds_base + LDS_BYTES + SIDE_LDS;
+    for (int c = wave; c < BM / 64; c += 4)
+      glds4_sv_m0(rowStats, 4u * (uint32_t)min(m0 + 64 * c + lane, M - 1), sb + 256 * c);
+    for (int c = wave; c < BN / 64; c += 4)
+      glds4_sv_m0(colStats, 4u * (uint32_t)min(n0 + 64 * c + lane, N - 1), sb + 4 * BM + 256 * c);
+    if (bias != nullptr && (N & 1) == 0)                 // bias as fp16 pairs (whole dwords: N even)
+      for (int c = wave; c < BN / 128; c += 4)
+        glds4_sv_m0(bias, 4u * (uint32_t)min(n0 / 2 + 64 * c + lane, N / 2 - 1), sb + 4 * BM + 4 * BN + 256 * c);
   }
+#pragma unroll
+  for (int i = 0; i < WI; ++i) dma_a(0, 0, i);
+#pragma unroll
+  for (int i = 0; i < WJ; ++i) dma_b(0, 0, i);
+  const int k1 = min(1, nk - 1);
+#pragma unroll
+  for (int i = 0; i < WI; ++i) dma_a(k1, 1, i);
+#pragma unroll
+  for (int i = 0; i < WJ; ++i) dma_b(k1, 1, i);
+  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(WI + WJ) : "memory");   // tile 0 landed; tile 1 in flight
+  if constexpr (SIDE) __builtin_amdgcn_s_waitcnt(0xC07F);          // (the side tables' LDS writes)
+  __builtin_amdgcn_s_barrier();
   if constexpr (TL) tl1 = hg_now();
 #pragma unroll
   for (int f = 0; f < WJ; ++f) w0[f] = rd(0, wo0, f);
 #pragma unroll
   for (int f = 0; f < WI; ++f) x0[f] = rd(0, xo0, f);
 
-  if constexpr ((V & 8192) != 0) {
-    if (nk == 1) {
-      tile3(std::true_type{}, std::true_type{}, 0);
-    } else {
-      tile3(std::true_type{}, std::false_type{}, 0);
-      for (int t = 1; t + 1 < nk; ++t) tile3(std::false_type{}, std::false_type{}, t);
-      tile3(std::false_type{}, std::true_type{}, nk - 1);
-    }
+  if (nk == 1) {
+    tile3(std::true_type{}, std::true_type{}, 0);
   } else {
-    half1(std::true_type{}, 0);
-    for (int t = 0; t + 1 < nk; ++t) {
-      half2(std::false_type{}, t, t & 1);
-      half1(std::false_type{}, t + 1);
-    }
-    half2(std::true_type{}, nk - 1, (nk - 1) & 1);
+    tile3(std::true_type{}, std::false_type{}, 0);
+    for (int t = 1; t + 1 < nk; ++t) tile3(std::false_type{}, std::false_type{}, t);
+    tile3(std::false_type{}, std::true_type{}, nk - 1);
   }
-  wait_vmcnt0();                                          // no LDS-DMA may outlive the workgroup
+  wait_vmcnt0();                                         // no LDS-DMA may outlive the workgroup
   if constexpr (TL) tl2 = hg_now();
   // MFMA (asm, invisible to hipcc's hazard recognizer) -> v_accvgpr_read: pad the wait states by hand
   __builtin_amdgcn_sched_barrier(0);
@@ -991,12 +719,7 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
   // loop has no register to spare for them)
   const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
   const int mb = m0 + 16 * WI * wm + (lane_e & 15), nb = n0 + 16 * WJ * wn + 4 * (lane_e >> 4);
-  constexpr int OUT = (OP == HG_I8_I32) ? 4 : 2;
-  const bool full = (m0 + BM <= M) && (n0 + BN <= N) && (((ldc * OUT) & 15) == 0) &&
-                    (((uintptr_t)Cv & 15) == 0);
-  auto value = [&](int j, int i, int r, int n, float rs) -> float {   // HG_I8_DEQ: mm_dequant of one element
-    return (float)Io<fp16_t>::to_f32(mm_dequant_value(acc[j][i][r], rs, colStats[n], bias ? (float)bias[n] : 0.0f));
-  };
+  const bool full = (m0 + BM <= M) && (n0 + BN <= N) && (((ldc * 2) & 15) == 0) && (((uintptr_t)Cv & 15) == 0);
   if constexpr (SPLIT) {
     // fp32 partials of this split: acc[j][i] = C[mb + 16 i][nb + 16 j .. +3], one 16-B store each (N % 4 == 0 on the
     // host rule), rows / columns past the edge skipped
@@ -1024,7 +747,7 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
         }
       }
     }
-  } else if (full && OUT == 2) {
+  } else if (full) {
     // 16-bit outputs of a full tile: staged through LDS so every global store writes whole 256-B row segments
     // (direct 8-B fragment stores put 16 rows x 32 B in one instruction: +4 us of epilogue per launch at 4096^2)
     __syncthreads();                                   // every wave is past its last stage read
@@ -1132,20 +855,9 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
 #pragma unroll 8
       for (int it = 0; it < 16 * WI / RPI; ++it) store_rows(it);
     }
-  } else if (full) {
-    if constexpr (OP == HG_I8_I32) {                   // int32: one 16-B store per accumulator already
-#pragma unroll
-      for (int i = 0; i < WI; ++i) {
-        const long long m = mb + 16 * i;
-#pragma unroll
-        for (int j = 0; j < WJ; ++j) {
-          const int n = nb + 16 * j;
-          *reinterpret_cast<hg_i32x4_t*>(reinterpret_cast<int32_t*>(Cv) + m * ldc + n) = acc[j][i];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-  } else {
+  } else if (!full) {
+    // (the second test of `full` is redundant and deliberate: with a plain `else` hipcc merges the two tests and
+    // re-allocates the epilogue's registers in every unsplit kernel -- a codegen change to measure on its own)
 #pragma unroll
     for (int i = 0; i < WI; ++i) {
       const int m = mb + 16 * i;
@@ -1160,16 +872,14 @@ k_hgemm(int M, int N, int K, const void* __restrict__ Av, long long lda, const v
           if (m < M && n < N) {
             if constexpr (OP == HG_BF16) reinterpret_cast<bf16_t*>(Cv)[mc * ldc + n] = Io<bf16_t>::from_f32(acc[j][i][r]);
             else if constexpr (OP == HG_FP16) reinterpret_cast<fp16_t*>(Cv)[mc * ldc + n] = Io<fp16_t>::from_f32(acc[j][i][r]);
-            else if constexpr (OP == HG_I8_DEQ)
+            else
               reinterpret_cast<fp16_t*>(Cv)[mc * ldc + n] =
                   mm_dequant_value(acc[j][i][r], rs, colStats[n], bias ? (float)bias[n] : 0.0f);
-            else reinterpret_cast<int32_t*>(Cv)[mc * ldc + n] = acc[j][i][r];
           }
           __builtin_amdgcn_sched_barrier(0);
         }
     }
   }
-  (void)value;
   if constexpr ((V & HG_V_TAIL) != 0) {
     // (a bare s_barrier, no fence: every wave is past its last LDS read -- the last k-tile's fragments fed its MFMAs,
     // its staging rows fed its stores -- before any wave writes its table over stage / staging bytes; a __syncthreads
@@ -1220,24 +930,31 @@ constexpr double HG_HALF_KT = 0.6;
 // chgemm_set_quarter_tile)
 static Knob<double> g_hg_quarter_kt{0.40};
 static Knob<int> g_hg_quarter{1};             // 0 = never, 1 = by cost (default), 2 = forced where allowed (tests / A-B)
+// One launch's view of the knobs: each is loaded once, when the launch (or a plan query) starts, and nothing below
+// reads a global again -- a setter on another thread changes the next launch, never the middle of this one.
+struct HgKnobs {
+  int side_mode, cwt, epi, quarter;
+  double quarter_kt;
+  static HgKnobs load() { return HgKnobs{g_side_mode, g_hg_cwt, g_hg_epi, g_hg_quarter, g_hg_quarter_kt}; }
+};
 struct HgPlan {
   int wi, wj, splits, kchunk;
 };
 int device_cu_count();   // CUs of the current device (cached; gemv4bit.hip)
-static HgPlan hgemm_plan(int m, int n, int k, int elem, bool allow_split, bool full_tiles_only,
+static HgPlan hgemm_plan(const HgKnobs& kn, int m, int n, int k, int elem, bool allow_split, bool full_tiles_only,
                          bool allow_quarter = false) {
   const int nkt = (int)((long long)k * elem / 128);
   int cus = device_cu_count();
   if (cus <= 0) cus = 256;
   const double part_kt = (double)m * n * 8.0 / 5.0e12 / 1.37e-6;   // one split's partial traffic, in k-tile times
   static const int shapes[4][2] = {{8, 8}, {8, 4}, {4, 8}, {4, 4}};
-  const bool quarter = allow_quarter && !full_tiles_only && g_hg_quarter != 0;
-  const bool forced = quarter && g_hg_quarter == 2;
+  const bool quarter = allow_quarter && !full_tiles_only && kn.quarter != 0;
+  const bool forced = quarter && kn.quarter == 2;
   HgPlan best{8, 8, 1, nkt};
   double best_cost = 1e300;
   for (int si = forced ? 3 : 0; si < (full_tiles_only ? 1 : quarter ? 4 : 3); ++si) {
     const int wi = shapes[si][0], wj = shapes[si][1];
-    const double tkt = (wi == 8 && wj == 8) ? 1.0 : (wi == 4 && wj == 4) ? g_hg_quarter_kt.load() : HG_HALF_KT;
+    const double tkt = (wi == 8 && wj == 8) ? 1.0 : (wi == 4 && wj == 4) ? kn.quarter_kt : HG_HALF_KT;
     const long long tiles = (long long)((m + 32 * wi - 1) / (32 * wi)) * ((n + 32 * wj - 1) / (32 * wj));
     double cost = (double)((tiles + cus - 1) / cus) * nkt * tkt;
     if (cost < best_cost) {
@@ -1261,7 +978,8 @@ static HgPlan hgemm_plan(int m, int n, int k, int elem, bool allow_split, bool f
 long long hgemm_workspace_bytes(int m, int n, int k, int elem) {
   // the larger of the plans with and without the 128 x 128 tile: a side-dequantise launch (chgemm_tn_pf_*) plans
   // without it and must find its partials' room too
-  const HgPlan pq = hgemm_plan(m, n, k, elem, true, false, elem == 2), pn = hgemm_plan(m, n, k, elem, true, false, false);
+  const HgKnobs kn = HgKnobs::load();
+  const HgPlan pq = hgemm_plan(kn, m, n, k, elem, true, false, elem == 2), pn = hgemm_plan(kn, m, n, k, elem, true, false, false);
   const int splits = std::max(pq.splits, pn.splits);
   return splits > 1 ? (long long)splits * m * n * (long long)sizeof(float) : 0;
 }
@@ -1286,25 +1004,25 @@ static void hgemm_launch_side(const HgPlan& pl, int m, int n, int k, const void*
 
 // false: a side dequantise was asked for that this kind / shape does not run (nothing launched)
 template <int OP, int V, int WI, int WJ>
-static bool hgemm_launch_shape(const HgPlan& pl, int m, int n, int k, const void* A, long long lda, const void* B,
-                               long long ldb, void* C, long long ldc, const float* rowStats, const float* colStats,
-                               const fp16_t* bias, float* ws, const HgSide* side) {
+static bool hgemm_launch_shape(const HgKnobs& kn, const HgPlan& pl, int m, int n, int k, const void* A, long long lda,
+                               const void* B, long long ldb, void* C, long long ldc, const float* rowStats,
+                               const float* colStats, const fp16_t* bias, float* ws, const HgSide* side) {
   // the tail form (default, round 6): the launched 16-bit kind, every tile shape; chgemm_set_side_mode(128 | ...) keeps
   // the round-4 in-loop form below
   if constexpr ((OP == HG_BF16 || OP == HG_FP16) && V == (HG_V | HG_V_CWT | HG_V_EPI)) {
-    if (side && !(g_side_mode & 128)) {
+    if (side && !(kn.side_mode & 128)) {
       HgSide sd = *side;
-      sd.mode = g_side_mode;
+      sd.mode = kn.side_mode;
       hgemm_launch_side<OP, V | HG_V_TAIL, WI, WJ, false>(pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias,
                                                           ws, sd);
       return true;
     }
   }
-  if constexpr ((OP == HG_BF16 || OP == HG_FP16) && (V & 8192) != 0 && !(WI == 4 && WJ == 4)) {
+  if constexpr ((OP == HG_BF16 || OP == HG_FP16) && !(WI == 4 && WJ == 4)) {
     if (side) {
       const long long wgs = (long long)((m + 32 * WI - 1) / (32 * WI)) * ((n + 32 * WJ - 1) / (32 * WJ)) * pl.splits;
       HgSide sd = *side;
-      sd.mode = g_side_mode;
+      sd.mode = kn.side_mode;
       const long long per = (sd.ndw + wgs - 1) / wgs;
       sd.iters = (int)((per + 4 * HG_THREADS - 1) / (4 * HG_THREADS));   // 4 dwords per lane per iteration
       sd.per_wg = sd.iters * 4 * HG_THREADS;
@@ -1335,38 +1053,39 @@ int hgemm_launch(int m, int n, int k, const void* A, long long lda, const void* 
   if (side && !FP) return 1;
   // (the 128 x 128 tile: 16-bit kinds without a side dequantise or with its tail form -- the in-loop form is not built
   // for it)
-  const bool quarter = FP && (side == nullptr || (!(g_side_mode & 128) && g_hg_cwt == 1 && g_hg_epi));
-  HgPlan pl = hgemm_plan(m, n, k, HgOpT<OP>::ELEM, FP, full_only, quarter);
+  const HgKnobs kn = HgKnobs::load();
+  const bool quarter = FP && (side == nullptr || (!(kn.side_mode & 128) && kn.cwt == 1 && kn.epi));
+  HgPlan pl = hgemm_plan(kn, m, n, k, HgOpT<OP>::ELEM, FP, full_only, quarter);
   if (pl.splits > 1 && (ws == nullptr || ((uintptr_t)ws & 15) ||
                         ws_bytes < (long long)pl.splits * m * n * (long long)sizeof(float)))
-    pl = hgemm_plan(m, n, k, HgOpT<OP>::ELEM, false, full_only, quarter);   // no (large enough) workspace: no split
+    pl = hgemm_plan(kn, m, n, k, HgOpT<OP>::ELEM, false, full_only, quarter);   // no (large enough) workspace: no split
   // variant bits of the launched kernel: write-through C (g_hg_cwt) and the interleaved epilogue (g_hg_epi, with it)
   auto by_shape = [&](auto vtag) {
     constexpr int VV = decltype(vtag)::value;
     if (pl.wi == 8 && pl.wj == 8)
-      return hgemm_launch_shape<OP, VV, 8, 8>(pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
+      return hgemm_launch_shape<OP, VV, 8, 8>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
     if constexpr (FP) {
-      if (pl.wi == 8) return hgemm_launch_shape<OP, VV, 8, 4>(pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
-      if (pl.wj == 8) return hgemm_launch_shape<OP, VV, 4, 8>(pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
-      return hgemm_launch_shape<OP, VV, 4, 4>(pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
+      if (pl.wi == 8) return hgemm_launch_shape<OP, VV, 8, 4>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
+      if (pl.wj == 8) return hgemm_launch_shape<OP, VV, 4, 8>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
+      return hgemm_launch_shape<OP, VV, 4, 4>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias, ws, side);
     }
     return false;
   };
   bool launched = true;
 #ifdef BNB_LAB
-  if (FP && g_hg_tl_on && g_hg_cwt == 1 && g_hg_epi && pl.wi == 8 && pl.wj == 8 && !side) {   // lab timeline
+  if (FP && g_hg_tl_on && kn.cwt == 1 && kn.epi && pl.wi == 8 && pl.wj == 8 && !side) {   // lab timeline
     // (16-bit kinds only: on the int8 body the stamps' registers spilled)
     if constexpr (FP)
-      launched = hgemm_launch_shape<OP, HG_V | HG_V_CWT | HG_V_EPI | HG_V_TL, 8, 8>(pl, m, n, k, A, lda, B, ldb, C, ldc,
+      launched = hgemm_launch_shape<OP, HG_V | HG_V_CWT | HG_V_EPI | HG_V_TL, 8, 8>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc,
                                                                                   rowStats, colStats, bias, ws, nullptr);
   } else
 #endif
-  if (g_hg_cwt == 2 && g_hg_epi && pl.wi == 8 && pl.wj == 8) {   // the lab's nt arm: full tile only
-    launched = hgemm_launch_shape<OP, HG_V | HG_V_CWT | HG_V_EPI | HG_V_CNT, 8, 8>(pl, m, n, k, A, lda, B, ldb, C, ldc,
+  if (kn.cwt == 2 && kn.epi && pl.wi == 8 && pl.wj == 8) {   // the lab's nt arm: full tile only
+    launched = hgemm_launch_shape<OP, HG_V | HG_V_CWT | HG_V_EPI | HG_V_CNT, 8, 8>(kn, pl, m, n, k, A, lda, B, ldb, C, ldc,
                                                                                  rowStats, colStats, bias, ws, side);
-  } else if (g_hg_cwt && g_hg_epi) {
+  } else if (kn.cwt && kn.epi) {
     launched = by_shape(std::integral_constant<int, HG_V | HG_V_CWT | HG_V_EPI>{});
-  } else if (g_hg_cwt) {
+  } else if (kn.cwt) {
     launched = by_shape(std::integral_constant<int, HG_V | HG_V_CWT>{});
   } else {
     launched = by_shape(std::integral_constant<int, HG_V>{});
@@ -1388,9 +1107,9 @@ int hgemm_launch(int m, int n, int k, const void* A, long long lda, const void* 
 // 1 = not covered (the caller's kernels run), 2 = launch error
 int igemm_4wave(int m, int n, int k, const int8_t* A, long long lda, const int8_t* B, long long ldb, void* C,
                 long long ldc, bool dequant, const float* rowStats, const float* colStats, const fp16_t* bias) {
-  // HG_I8_I32 is not launched: its epilogue needs spill registers, and a spill the allocator places between the last
-  // (inline-asm, hazard-invisible) MFMAs and the wait-state pad reads accumulators before they are written (wrong
-  // int32 at ragged shapes, caught by tests/test_hgemm_gpu.py).  The launched kinds compile spill-free.
+  // the plain int32 product has no 4-wave kernel: its epilogue needed spill registers, and a spill the allocator places
+  // between the last (inline-asm, hazard-invisible) MFMAs and the wait-state pad reads accumulators before they are
+  // written (wrong int32 at ragged shapes).  The kinds that are built compile spill-free.
   if (!dequant) return 1;
   return hgemm_launch<HG_I8_DEQ>(m, n, k, A, lda, B, ldb, C, ldc, rowStats, colStats, bias);
 }
@@ -1473,13 +1192,12 @@ long long chgemm_tn_workspace_bytes(int m, int n, int k) { return bnb::hgemm_wor
 // k-tiles per split}; the output tile is 32 WI x 32 WJ (256 x 256, 256 x 128 or 128 x 256)
 void chgemm_tn_plan(int m, int n, int k, int* out) {
   BNB_RANGE("chgemm_tn_plan");
-  const bnb::HgPlan pl = bnb::hgemm_plan(m, n, k, 2, true, false, true);
+  const bnb::HgPlan pl = bnb::hgemm_plan(bnb::HgKnobs::load(), m, n, k, 2, true, false, true);
   out[0] = pl.wi;
   out[1] = pl.wj;
   out[2] = pl.splits;
   out[3] = pl.kchunk;
 }
-// [additive, testing] the side dequantise's A/B bits (HgSide::mode); returns the previous setting
 // [additive, testing] 1 (default): k_hgemm stores C and its split-K partials write-through (sc1), 0: write-back;
 // 2: write-through + non-temporal (the 256 x 256 tile's interleaved epilogue; others as 1); returns the previous setting
 int chgemm_set_c_store(int wt) {
@@ -1517,8 +1235,10 @@ int chgemm_set_epilogue(int v) {
   bnb::g_hg_epi = v ? 1 : 0;
   return prev;
 }
-// [additive, testing] the side dequantise's load / store hint: bit 1 = non-temporal (default); the lab build also takes
-// its ablation bits (2 / 8 / 16 / 32 / 64: wrong weights, timing only), the product library masks them off
+// [additive, testing] the side dequantise's form and hint: bit 128 = the in-loop form (default: the tail form); bit 1
+// (default) = non-temporal side loads / stores of the in-loop form, which alone reads it (the tail form always loads
+// non-temporally and stores write-through); the lab build also takes the in-loop form's ablation bits (2 / 8 / 16 / 32 /
+// 64: wrong weights, timing only), the product library masks them off
 int chgemm_set_side_mode(int v) {
   BNB_RANGE("chgemm_set_side_mode");
   const int prev = bnb::g_side_mode;

@@ -288,8 +288,11 @@ int cdequantize_set_store_policy(int policy);
  * scalar loads (1, where blocksize 64 / blocksize2 >= 64 / 64-B aligned codes allow) or per lane (0, default: measured
  * faster); bit-identical; returns the previous setting */
 int cdequantize_set_nested_scalar(int on);
-/* [additive, testing] k_hgemm side dequantise (chgemm_tn_pf_*): bit 1 (default) = non-temporal side loads / stores,
- * 0 = plain; other bits are ignored (the lab build's ablations); returns the previous value */
+/* [additive, testing] k_hgemm side dequantise (chgemm_tn_pf_*): bit 128 selects the in-loop form (side steps between
+ * the MFMAs of the k-loop); clear (default) = the tail form (each wave dequantises its share after its tile's epilogue).
+ * Bit 1 (set by default) applies to the in-loop form only: non-temporal side loads / stores, clear = plain ones.  The
+ * tail form always loads non-temporally and stores device-scope write-through, whatever bit 1 says.  Other bits are
+ * ignored (the lab build's ablations); returns the previous value */
 int chgemm_set_side_mode(int v);
 /* [additive, testing] 1 (default): k_hgemm stores C and its split-K partials write-through (device scope), 0:
  * write-back, 2: write-through + non-temporal hint (256 x 256 tile, interleaved epilogue; others as 1); returns the

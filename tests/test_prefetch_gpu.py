@@ -58,8 +58,8 @@ def _pf_gemm(X, W, pf):
     return out, target.view(sn.shape[0], sn.shape[1])
 
 
-# the two side-dequantise forms: 1 = the tail form (default since round 6: after the tile's epilogue, chunks taken by
-# work stealing), 129 = the round-4 in-loop form (side steps between the MFMAs); both non-temporal side loads
+# the two side-dequantise forms: 1 = the tail form (default since round 6: after the tile's epilogue, chunk c going to
+# wave c mod waves, no counter), 129 = the round-4 in-loop form (side steps between the MFMAs); both non-temporal side loads
 FORMS = [1, 129]
 
 

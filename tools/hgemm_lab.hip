@@ -1,6 +1,7 @@
 // LAB (not built into the library): csrc/hgemm.hip (hand-written 4-wave 256x256 bf16 GEMM) against rocBLAS's
 // standard algorithm on the same operands: agreement (fp32-accumulated references, bf16 outputs) and timing,
 // interleaved rounds in one process (cdna_hip_programming.md §5.4 rule 24).  Operands uniform [-1, 1) random.
+// Build: LABFLAGS="-fno-slp-vectorize -lrocblas" bash tools/labbuild.sh hgemm_lab
 // Usage: hgemm_lab [M N K] [rounds]
 #define ROCBLAS_BETA_FEATURES_API
 #pragma clang diagnostic ignored "-Wdeprecated-declarations"
@@ -18,7 +19,7 @@
 namespace bnb {
 hipStream_t current_stream() { return nullptr; }
 void set_error(int, const char* what) { printf("error: %s\n", what); }
-int g_tile_override = 0;
+Knob<int> g_tile_override{0};
 BnbRange::BnbRange(const char*) : on(false) {}
 BnbRange::~BnbRange() {}
 int device_cu_count() { return 256; }
@@ -32,11 +33,12 @@ using namespace bnb;
 
 static float bf2f(uint16_t v) { uint32_t u = (uint32_t)v << 16; float f; memcpy(&f, &u, 4); return f; }
 
-// the k_hgemm schedule variants compared (HG_V bits, csrc/hgemm.hip)
+// the k_hgemm variants compared (feature bits on HG_V, csrc/hgemm.hip): the plain kernel (round-4 epilogue, write-back
+// C) and the launched one (write-through C, interleaved epilogue)
 template <int... Vs> struct Variants {
   template <class F> static void each(F f) { (f(std::integral_constant<int, Vs>{}), ...); }
 };
-using LabV = Variants<16 + 8192, 8 + 16 + 4096>;
+using LabV = Variants<HG_V, HG_V | HG_V_CWT | HG_V_EPI>;
 
 int main(int argc, char** argv) {
   const int M = argc > 1 ? atoi(argv[1]) : 4096, N = argc > 2 ? atoi(argv[2]) : 4096, K = argc > 3 ? atoi(argv[3]) : 11008;
