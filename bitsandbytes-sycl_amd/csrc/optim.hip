@@ -6,6 +6,9 @@
 //                    C-ABI c<name>_8bit_blockwise_grad_<T> ref:sycl/pythonInterface.cpp:264-284
 //   32-bit           kOptimizer32bit2State / 1State       ref:sycl/sycl_code/kernel_quant.cpp:1614-2060
 //                    C-ABI c<name>32bit_grad_<T>          ref:sycl/pythonInterface.cpp:223-241
+//   norms            kPercentileClipping                  ref:sycl/sycl_code/kernel_quant.cpp:2653-2703
+//                    kPreconditionOptimizer32bit{2,1}State ref:sycl/sycl_code/kernel_quant.cpp:1500-1608, 1775-1880
+//                    C-ABI cpercentile_clipping_g<T>      ref:sycl/pythonInterface.cpp:284-285
 //
 // Semantics are the reference's formulas, op for op in fp32 (build: -ffp-contract=off), with the
 // intended behaviour where the reference is defective:
@@ -16,7 +19,10 @@
 //     LION 5); the reference's kernel switches on 1/2/3/4, so ADAGRAD runs the Lion update and LION
 //     runs none (Q22);
 //   * tail elements of the last 2048-block are loaded as the upstream defaults (g = 0, state1 code
-//     128, state2 code 0) and never stored; the reference loads past n (Q2-style, Q23).
+//     128, state2 code 0) and never stored; the reference loads past n (Q2-style, Q23);
+//   * the gradient and update norms are fixed-order fp64 sums that overwrite their destination; the
+//     reference accumulates them with float atomics (Q24) into a float it zeroes first, for unorm
+//     with std::memset on the device pointer (Q25); max_unorm is refused for Lion and Adagrad (Q26, Q27).
 // sqrt is __builtin_sqrtf, which hipcc lowers to the correctly rounded sequence (v_sqrt_f32 + two fma
 // residual checks); __fsqrt_rn lowers to the bare 1-ulp v_sqrt_f32 on ROCm 7.2.
 // The bias corrections are computed once on the host in double (the reference's pow(float, int)
@@ -35,6 +41,8 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <mutex>
+#include <vector>
 
 namespace bnb {
 
@@ -344,13 +352,120 @@ k_optimizer_8bit_blockwise_1state(T* __restrict__ p, const T* __restrict__ g, ui
   }
 }
 
+// ---------------------------------------------------------------- deterministic sums of squares
+// The full-tensor L2 norms ahead of the element-wise update: the gradient norm of percentile clipping
+// (kPercentileClipping, kernel_quant.cpp:2653-2703) and the norm of the trial update of max_unorm
+// (kPreconditionOptimizer32bit{2,1}State, kernel_quant.cpp:1500-1608, 1775-1880).  The reference adds
+// one fp32 partial per workgroup into a single float with an atomic, so its sum depends on the order
+// in which workgroups retire.  Here the summation order is a function of n alone:
+//
+//   1. the tensor is cut into chunks of NORM_CHUNK = 4096 elements; slot b (0 <= b < NORM_SLOTS = 1024)
+//      takes chunks b, b + 1024, b + 2048, ... in that order.  Workgroup b of k_sumsq_partials owns
+//      slot b; the grid is min(chunks, 1024), whatever the device.
+//   2. inside a chunk, thread t (0..255) takes elements [8t, 8t + 8) and then [2048 + 8t, 2048 + 8t + 8),
+//      each group in index order, and adds every term to one fp64 accumulator as it goes (elements
+//      at or past n add +0.0).  A term is the exact fp64 square of the gradient, or the fp32 square of
+//      the trial update converted to fp64.
+//   3. the 256 accumulators of a workgroup are summed by wg_sum256: in each wave a butterfly over lane
+//      distances 32, 16, 8, 4, 2, 1 (lane i adds the value of lane i ^ d; fp addition commutes, so all
+//      lanes hold the same bits), then (w0 + w1) + (w2 + w3) over the four waves.  Thread 0 writes the
+//      slot with a plain store.
+//   4. k_sumsq_finish, one workgroup on the same stream: thread t adds slots t, t + 256, t + 512,
+//      t + 768 in that order, the same wg_sum256 follows, and the total is rounded once to fp32.
+//
+// No atomics anywhere.  The slots (8 KB of fp64) live in a workspace the library owns per (device,
+// stream): launches on one stream are ordered, two streams never share slots.  The finishing step is a
+// launch of its own rather than a prologue of every update workgroup; that A/B and the achieved
+// bandwidth (fp32, 2^24 elements: 5.7 TB/s, 71 % of HBM peak) are in DESIGN.md §4.
+constexpr int NORM_CHUNK = 4096, NORM_SLOTS = 1024;
+constexpr int NORM_GRAD = -1;                      // the kind beside ADAM / MOMENTUM / RMSPROP
+
+struct NormScalars {
+  float beta1, beta2, eps, gnorm_scale;
+  float pc1, pc2;       // Adam's 1 / (1 - beta^step), kernel_quant.cpp:1522-1523
+  int step;
+};
+
+__device__ __forceinline__ double wg_sum256(double v, double* xch) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  if ((threadIdx.x & 63) == 0) xch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (xch[0] + xch[1]) + (xch[2] + xch[3]);
+}
+
+template <typename T, int KIND>
+__global__ void __launch_bounds__(OPT_THREADS)
+k_sumsq_partials(const T* __restrict__ g, const float* __restrict__ state1, const float* __restrict__ state2,
+                 NormScalars k, int n, double* __restrict__ partials) {
+  __shared__ double xch[4];
+  const long long chunks = ((long long)n + NORM_CHUNK - 1) / NORM_CHUNK;
+  double acc = 0.0;
+  for (long long c = blockIdx.x; c < chunks; c += NORM_SLOTS) {
+    const long long i0 = c * NORM_CHUNK + (long long)threadIdx.x * OPT_NPT;
+    float gv[2][8], s1[2][8], s2[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                  // both halves' loads in flight before the arithmetic
+      load8(g, i0 + h * OPT_BLOCK, n, gv[h], 0.0f);
+      if (KIND != NORM_GRAD) load8(state1, i0 + h * OPT_BLOCK, n, s1[h], 0.0f);
+      if (KIND == ADAM) load8(state2, i0 + h * OPT_BLOCK, n, s2[h], 0.0f);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        double term;
+        if (KIND == NORM_GRAD) {
+          const double d = (double)gv[h][j];
+          term = d * d;                            // exact: 48 significant bits
+        } else {
+          // op for op kernel_quant.cpp:1577-1590 (two states), 1834-1855 (one state); no weight decay and no
+          // skip_zeros in the precondition, as there
+          const float gt = Io<T>::to_f32(Io<T>::from_f32(__fmul_rn(k.gnorm_scale, gv[h][j])));
+          float u;
+          if (KIND == ADAM) {
+            float a = __fadd_rn(__fmul_rn(s1[h][j], k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), gt));
+            float b = __fadd_rn(__fmul_rn(s2[h][j], k.beta2), __fmul_rn(__fsub_rn(1.0f, k.beta2), __fmul_rn(gt, gt)));
+            a = __fmul_rn(a, k.pc1);
+            b = __fmul_rn(b, k.pc2);
+            u = __fdiv_rn(a, __fadd_rn(__builtin_sqrtf(b), k.eps));
+          } else if (KIND == MOMENTUM) {
+            u = (k.step == 1) ? gt : __fadd_rn(__fmul_rn(s1[h][j], k.beta1), gt);
+          } else {   // RMSPROP
+            const float a = __fadd_rn(__fmul_rn(s1[h][j], k.beta1), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, k.beta1), gt), gt));
+            u = __fdiv_rn(gt, __fadd_rn(__builtin_sqrtf(a), k.eps));
+          }
+          term = (double)__fmul_rn(u, u);
+        }
+        acc += (i0 + h * OPT_BLOCK + j < n) ? term : 0.0;
+      }
+    }
+  }
+  const double total = wg_sum256(acc, xch);
+  if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+// sums the slots and writes (float)total to out[first .. first + count), count <= 256
+__global__ void __launch_bounds__(OPT_THREADS)
+k_sumsq_finish(const double* __restrict__ partials, int slots, float* __restrict__ out, int first, int count) {
+  __shared__ double xch[4];
+  double acc = 0.0;
+  for (int s = threadIdx.x; s < slots; s += OPT_THREADS) acc += partials[s];
+  const double total = wg_sum256(acc, xch);
+  if ((int)threadIdx.x < count) out[first + threadIdx.x] = (float)total;
+}
+
 // ---------------------------------------------------------------- 32-bit states
-// kOptimizer32bit2State / 1State with max_unorm == 0 (update_scale == 1); gradients are rounded to
-// T after scaling (and after weight decay for one state), as the reference keeps them in g_vals.
+// kOptimizer32bit2State / 1State; gradients are rounded to T after scaling (and after weight decay for
+// one state), as the reference keeps them in g_vals.  update_scale (kernel_quant.cpp:1635-1641,
+// 1897-1903) is formed on the device from unorm[0], which k_sumsq_finish wrote on this stream, after
+// the thread's loads are issued (its square root and division then hide behind them; ahead of the loads
+// they cost the max_unorm == 0 path 1 %); `bound` is max_unorm * param_norm (+ eps for one state).
+// unorm == nullptr (max_unorm == 0) gives 1.0f, and the products by it are exact.
 template <typename T, int OPT>
 __global__ void __launch_bounds__(OPT_THREADS)
 k_optimizer_32bit(T* __restrict__ p, const T* __restrict__ g, float* __restrict__ state1, float* __restrict__ state2,
-                  OptScalars k, int n) {
+                  OptScalars k, const float* __restrict__ unorm, float bound, int n) {
   const long long i0 = ((long long)blockIdx.x * OPT_THREADS + threadIdx.x) * OPT_NPT;
   if (i0 >= n) return;
   float gv[8], pv[8], s1[8], s2[8];
@@ -358,6 +473,11 @@ k_optimizer_32bit(T* __restrict__ p, const T* __restrict__ g, float* __restrict_
   load8(p, i0, n, pv, 0.0f);
   load8(state1, i0, n, s1, 0.0f);
   if (OPT == ADAM) load8(state2, i0, n, s2, 0.0f);
+  float update_scale = 1.0f;
+  if (unorm != nullptr) {
+    const float un = __builtin_sqrtf(unorm[0]);
+    if (un > bound) update_scale = __fdiv_rn(bound, un);
+  }
   T po[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -369,17 +489,18 @@ k_optimizer_32bit(T* __restrict__ p, const T* __restrict__ g, float* __restrict_
         s1[j] = __fadd_rn(__fmul_rn(s1[j], k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), gt));
         s2[j] = __fadd_rn(__fmul_rn(s2[j], k.beta2), __fmul_rn(__fsub_rn(1.0f, k.beta2), __fmul_rn(gt, gt)));
         pn = Io<T>::to_f32(Io<T>::from_f32(
-            __fadd_rn(pv[j], __fmul_rn(k.step_size, __fdiv_rn(s1[j], __fadd_rn(__builtin_sqrtf(s2[j]), k.c2eps))))));
+            __fadd_rn(pv[j], __fmul_rn(__fmul_rn(update_scale, k.step_size),
+                                       __fdiv_rn(s1[j], __fadd_rn(__builtin_sqrtf(s2[j]), k.c2eps))))));
         if (k.weight_decay > 0.0f) pn = __fmul_rn(pn, k.decay);
       } else if (OPT == MOMENTUM) {
         s1[j] = (k.step == 1) ? gt : __fadd_rn(__fmul_rn(s1[j], k.beta1), gt);
-        pn = __fadd_rn(pv[j], -__fmul_rn(k.lr, s1[j]));
+        pn = __fadd_rn(pv[j], __fmul_rn(update_scale, -__fmul_rn(k.lr, s1[j])));
       } else if (OPT == LION) {
         pn = __fsub_rn(pv[j], __fmul_rn(k.lr, sgnf(__fadd_rn(__fmul_rn(s1[j], k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), gt)))));
         s1[j] = __fadd_rn(__fmul_rn(s1[j], k.beta2), __fmul_rn(__fsub_rn(1.0f, k.beta2), gt));
       } else if (OPT == RMSPROP) {
         s1[j] = __fadd_rn(__fmul_rn(s1[j], k.beta1), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, k.beta1), gt), gt));
-        pn = __fsub_rn(pv[j], __fdiv_rn(__fmul_rn(k.lr, gt), __fadd_rn(__builtin_sqrtf(s1[j]), k.eps)));
+        pn = __fsub_rn(pv[j], __fmul_rn(update_scale, __fdiv_rn(__fmul_rn(k.lr, gt), __fadd_rn(__builtin_sqrtf(s1[j]), k.eps))));
       } else {   // ADAGRAD
         s1[j] = __fadd_rn(s1[j], __fmul_rn(gt, gt));
         pn = __fsub_rn(pv[j], __fdiv_rn(__fmul_rn(k.lr, gt), __fadd_rn(__builtin_sqrtf(s1[j]), k.eps)));
@@ -445,20 +566,93 @@ void optimizer_8bit_blockwise(T* p, T* g, uint8_t* state1, uint8_t* state2, floa
   BNB_LAUNCH_CHECK("optimizer_8bit_blockwise");
 }
 
+// The fp64 slots of the sums of squares: one 8 KB buffer per (device, stream), allocated on first use and kept for
+// the life of the process.  A stream that is capturing a graph cannot allocate; it needs a buffer from an earlier
+// (eager) call on that stream.
+static double* norm_workspace(hipStream_t stream) {
+  struct Entry { int dev; hipStream_t stream; double* ptr; };
+  static std::mutex mu;
+  static std::vector<Entry> entries;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lk(mu);
+  for (const Entry& e : entries)
+    if (e.dev == dev && e.stream == stream) return e.ptr;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+    (void)hipGetLastError();
+    set_error(1, "optimizer norm: no workspace for this stream yet and the stream is capturing a graph "
+                 "(run one step on the stream before the capture)");
+    return nullptr;
+  }
+  double* ptr = nullptr;
+  if (hipMalloc(&ptr, NORM_SLOTS * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error(2, "optimizer norm: workspace allocation failed");
+    return nullptr;
+  }
+  entries.push_back({dev, stream, ptr});
+  return ptr;
+}
+
+// out[first .. first + count) = (float)(sum of the KIND terms over n elements); false when nothing was written
+template <typename T, int KIND>
+static bool sumsq(const T* g, const float* state1, const float* state2, const NormScalars& k, int n, float* out,
+                  int first, int count) {
+  const hipStream_t stream = current_stream();
+  double* ws = norm_workspace(stream);
+  if (ws == nullptr) return false;
+  const int slots = n <= 0 ? 0 : (int)std::min<long long>(((long long)n + NORM_CHUNK - 1) / NORM_CHUNK, NORM_SLOTS);
+  if (slots > 0)
+    hipLaunchKernelGGL((k_sumsq_partials<T, KIND>), dim3(slots), dim3(OPT_THREADS), 0, stream, g, state1, state2, k, n,
+                       ws);
+  hipLaunchKernelGGL(k_sumsq_finish, dim3(1), dim3(OPT_THREADS), 0, stream, ws, slots, out, first, count);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error((int)e, "optimizer norm"); return false; }
+  return true;
+}
+
+template <typename T>
+void percentile_clipping(T* g, float* gnorm_vec, int step, int n) {
+  if (gnorm_vec == nullptr) { set_error(1, "percentile_clipping: gnorm_vec is null"); return; }
+  const bool all = step == 1;                      // the first step seeds every entry (kernel_quant.cpp:2691-2697)
+  sumsq<T, NORM_GRAD>(g, nullptr, nullptr, NormScalars{}, n, gnorm_vec, all ? 0 : ((step % 100) + 100) % 100,
+                      all ? 100 : 1);
+}
+
 template <typename T, int OPT>
 void optimizer_32bit(T* g, T* p, float* state1, float* state2, float* unorm, float max_unorm, float param_norm,
                      float beta1, float beta2, float eps, float weight_decay, int step, float lr, float gnorm_scale,
                      bool skip_zeros, int n) {
-  (void)unorm; (void)param_norm;
   if (n <= 0) return;
-  if (max_unorm > 0.0f) {
-    set_error(1, "optimizer32bit: max_unorm > 0 (update-norm clipping) is not supported by this build");
-    return;
-  }
   const OptScalars k = make_scalars(beta1, beta2, eps, step, lr, weight_decay, gnorm_scale, skip_zeros);
   const unsigned blocks = (unsigned)((n + OPT_THREADS * OPT_NPT - 1) / (OPT_THREADS * OPT_NPT));
+  const float* unorm_in = nullptr;
+  float bound = 0.0f;
+  if (max_unorm > 0.0f) {
+    if constexpr (OPT == LION) {
+      set_error(1, "optimizer32bit: max_unorm > 0 is refused for lion (the reference's precondition sums the "
+                   "unsquared state, so its update norm is a signed sum)");
+      return;
+    } else if constexpr (OPT == ADAGRAD) {
+      set_error(1, "optimizer32bit: max_unorm > 0 is refused for adagrad (the reference's update ignores the "
+                   "update scale)");
+      return;
+    } else {
+      if (unorm == nullptr) { set_error(1, "optimizer32bit: max_unorm > 0 needs unorm (one float)"); return; }
+      NormScalars ns{};
+      ns.beta1 = beta1; ns.beta2 = beta2; ns.eps = eps; ns.gnorm_scale = gnorm_scale; ns.step = step;
+      // 1.0f / (1.0f - pow(beta, step)) with pow(float, int) in double, rounded once (kernel_quant.cpp:1522-1523)
+      ns.pc1 = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)step)));
+      ns.pc2 = (float)(1.0 / (1.0 - std::pow((double)beta2, (double)step)));
+      const float mp = max_unorm * param_norm;
+      bound = (OPT == ADAM) ? mp : mp + eps;
+      if (!sumsq<T, OPT>(g, state1, state2, ns, n, unorm, 0, 1)) return;
+      unorm_in = unorm;
+    }
+  }
   hipLaunchKernelGGL((k_optimizer_32bit<T, OPT>), dim3(blocks), dim3(OPT_THREADS), 0, current_stream(), p, g, state1,
-                     state2, k, n);
+                     state2, k, unorm_in, bound, n);
   BNB_LAUNCH_CHECK("optimizer_32bit");
 }
 
@@ -519,5 +713,15 @@ BNB_FUNC32(lion, LION, bf16_t, bf16)
 BNB_FUNC32(adagrad, ADAGRAD, float, 32)
 BNB_FUNC32(adagrad, ADAGRAD, fp16_t, 16)
 BNB_FUNC32(adagrad, ADAGRAD, bf16_t, bf16)
+
+#define BNB_PERCENTILE_CLIPPING(gtype, gbits)                                                        \
+  void cpercentile_clipping_g##gbits(gtype* g, float* gnorm_vec, int step, const int n) {            \
+    BNB_RANGE("cpercentile_clipping_g" #gbits);                                                      \
+    percentile_clipping<gtype>(g, gnorm_vec, step, n);                                               \
+  }
+// ref:sycl/pythonInterface.cpp:284-285 + the bf16 sibling (additive)
+BNB_PERCENTILE_CLIPPING(float, 32)
+BNB_PERCENTILE_CLIPPING(fp16_t, 16)
+BNB_PERCENTILE_CLIPPING(bf16_t, bf16)
 
 }  // extern "C"

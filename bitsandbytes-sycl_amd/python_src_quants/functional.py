@@ -1684,6 +1684,9 @@ _OPT_NAMES = ("adam", "momentum", "rmsprop", "adagrad", "lion")
 _SUFFIX32 = {"adam": ("fp32", "fp16", "bf16"), "momentum": ("32", "16", "bf16"), "rmsprop": ("32", "16", "bf16"),
              "adagrad": ("32", "16", "bf16"), "lion": ("fp32", "fp16", "bf16")}
 _DTYPE_INDEX = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+# optimizers whose max_unorm the backend refuses, with the reason
+_NO_UNORM = {"lion": "the reference's precondition sums the unsquared state, so its update norm is a signed sum",
+             "adagrad": "the reference's update ignores the update scale"}
 
 
 def _opt_fn(optimizer_name: str, g: Tensor, blockwise: bool):
@@ -1723,11 +1726,19 @@ def optimizer_update_32bit(optimizer_name: str, g: Tensor, p: Tensor, state1: Te
                            unorm_vec: Optional[torch.Tensor] = None, max_unorm: float = 0.0,
                            skip_zeros=False) -> None:
     """In-place optimizer step with fp32 states (ref:functional.py:1526-1615 -> c<name>32bit_grad_<T>).
-    max_unorm > 0 (update-norm clipping, kPreconditionOptimizer32bit) is not supported here."""
-    if max_unorm > 0.0:
-        raise NotImplementedError("max_unorm > 0 is not supported by the MI355X backend")
-    optim_func = _opt_fn(optimizer_name, g, False)
+
+    max_unorm > 0 (adam / lamb, momentum, rmsprop) clips the L2 norm of the update against
+    max_unorm * ||p||: the call overwrites unorm_vec[0] (one fp32) with the squared norm of this step's
+    trial update, a fixed-order reduction on the device, and the update kernel reads it there."""
     param_norm = 0.0
+    if max_unorm > 0.0:
+        if optimizer_name in _NO_UNORM:
+            raise NotImplementedError(f"max_unorm > 0 is not supported for {optimizer_name}: "
+                                      f"{_NO_UNORM[optimizer_name]}")
+        if unorm_vec is None:
+            raise ValueError("max_unorm > 0 needs unorm_vec (one fp32 element on the gradient's device)")
+        param_norm = torch.norm(p.data.float()).item()
+    optim_func = _opt_fn(optimizer_name, g, False)
     is_on_gpu([g, p, state1, state2, unorm_vec])
     prev_device = pre_call(g.device)
     optim_func(get_ptr(g), get_ptr(p), get_ptr(state1), get_ptr(state2), get_ptr(unorm_vec), ct.c_float(max_unorm),
@@ -1735,3 +1746,30 @@ def optimizer_update_32bit(optimizer_name: str, g: Tensor, p: Tensor, state1: Te
                ct.c_float(weight_decay), ct.c_int32(step), ct.c_float(lr), ct.c_float(gnorm_scale),
                ct.c_bool(skip_zeros), ct.c_int32(g.numel()))
     post_call(prev_device)
+
+
+_CLIP_SUFFIX = ("g32", "g16", "gbf16")
+
+
+def percentile_clipping(grad: Tensor, gnorm_vec: Tensor, step: int, percentile: int = 5):
+    """Percentile clipping (ref:functional.py:1817-1856 -> cpercentile_clipping_<T>).
+
+    gnorm_vec holds the squared L2 norms of the last 100 gradients (fp32, 100 elements).  The call
+    overwrites entry ``step % 100`` (every entry when ``step == 1``) with this gradient's squared norm, a
+    fixed-order fp64 reduction rounded once to fp32, so equal gradients give equal bits, and returns
+    (current_gnorm, clip_value, gnorm_scale): the norm, the ``percentile``-th smallest recorded norm, and
+    clip_value / current_gnorm when the norm exceeds it, else 1.0.  fp32, fp16 and bf16 gradients."""
+    if grad.dtype not in _DTYPE_INDEX:
+        raise ValueError(f"Gradient type {grad.dtype} not supported!")
+    is_on_gpu([grad, gnorm_vec])
+    prev_device = pre_call(grad.device)
+    getattr(lib, "cpercentile_clipping_" + _CLIP_SUFFIX[_DTYPE_INDEX[grad.dtype]])(
+        get_ptr(grad), get_ptr(gnorm_vec), ct.c_int32(step), ct.c_int32(grad.numel()))
+    post_call(prev_device)
+    current_gnorm = torch.sqrt(gnorm_vec[step % 100])
+    vals, _ = torch.sort(gnorm_vec)
+    clip_value = torch.sqrt(vals[percentile])
+    gnorm_scale = 1.0
+    if current_gnorm > clip_value:
+        gnorm_scale = clip_value / current_gnorm
+    return current_gnorm, clip_value, gnorm_scale

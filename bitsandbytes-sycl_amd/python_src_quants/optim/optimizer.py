@@ -1,13 +1,21 @@
 """8-bit / 32-bit state optimizers, mirroring ref:python_src_quants/optim/optimizer.py.
 
 Optimizer8bit / Optimizer2State / Optimizer1State keep the reference's constructor arguments, state
-keys (step, state1, state2, qmap1, qmap2, absmax1, absmax2), GlobalOptimManager overrides and
-state_dict round trip.  Per parameter the update is one HIP launch:
+keys (step, state1, state2, qmap1, qmap2, absmax1, absmax2, gnorm_vec, unorm_vec), GlobalOptimManager
+overrides and state_dict round trip.  Per parameter the update is one HIP launch:
   * 8-bit blockwise states (optim_bits=8, block_wise=True, numel >= min_8bit_size):
     F.optimizer_update_8bit_blockwise -> c<name>_8bit_blockwise_grad_<T>;
   * fp32 states otherwise: F.optimizer_update_32bit -> c<name>32bit_grad_<T>.
+Two settings put a full-tensor L2 norm (a fixed-order reduction on the device, equal bits for equal
+inputs) ahead of it:
+  * percentile_clipping < 100 (both state kinds): F.percentile_clipping records the gradient's squared
+    norm in state["gnorm_vec"] (the last 100) and the update scales the gradient by its gnorm_scale;
+  * max_unorm > 0 (fp32 states; adam / lamb, momentum, rmsprop): the update's norm is clipped against
+    max_unorm * ||p||; its square is left in state["unorm_vec"].
 Not provided by this backend (they raise NotImplementedError): the non-blockwise 8-bit path
-(global max, kOptimizerStatic8bit2State), percentile clipping, max_unorm and paged state.
+(global max, kOptimizerStatic8bit2State), paged state, max_unorm with 8-bit blockwise state (the
+reference's blockwise kernel has no such input and drops the setting) and max_unorm for lion and
+adagrad (the reference's Lion norm is a signed sum, its Adagrad update ignores the scale).
 """
 from __future__ import annotations
 
@@ -223,11 +231,29 @@ class Optimizer8bit(torch.optim.Optimizer):
         if dtype == torch.uint8 and not config["block_wise"]:
             raise NotImplementedError("non-blockwise 8-bit optimizer state is not supported by the MI355X backend "
                                       "(use block_wise=True)")
-        if config["percentile_clipping"] < 100:
-            raise NotImplementedError("percentile_clipping < 100 is not supported by the MI355X backend")
         if config["max_unorm"] > 0.0:
-            raise NotImplementedError("max_unorm > 0 is not supported by the MI355X backend")
+            if dtype == torch.uint8:
+                raise NotImplementedError("max_unorm > 0 with 8-bit blockwise state is not supported by the MI355X "
+                                          "backend (the reference's blockwise kernel has no such input and would "
+                                          "drop the setting)")
+            if self.optimizer_name in F._NO_UNORM:
+                raise NotImplementedError(f"max_unorm > 0 is not supported for {self.optimizer_name}: "
+                                          f"{F._NO_UNORM[self.optimizer_name]}")
         return dtype
+
+    @staticmethod
+    def _norm_state(config, p, state):
+        """The norm records of percentile clipping and max_unorm (ref:optim/optimizer.py:475-479)."""
+        if config["percentile_clipping"] < 100:
+            state["gnorm_vec"] = torch.zeros((100,), device=p.device)
+        if config["max_unorm"] > 0.0:
+            state["unorm_vec"] = torch.zeros((1,), device=p.device)
+
+    @staticmethod
+    def _gnorm_scale(config, grad, state, step):
+        if config["percentile_clipping"] < 100:
+            return F.percentile_clipping(grad, state["gnorm_vec"], step, config["percentile_clipping"])[2]
+        return 1.0
 
     def _qmaps(self, p):
         if "dynamic" not in self.name2qmap:
@@ -292,6 +318,7 @@ class Optimizer2State(Optimizer8bit):
             blocks = self._blocks(p)
             state["absmax1"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
             state["absmax2"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
+        self._norm_state(config, p, state)
 
     @torch.no_grad()
     def update_step(self, group, p, gindex, pindex):
@@ -302,16 +329,18 @@ class Optimizer2State(Optimizer8bit):
         config = self.get_config(gindex, pindex, group)
         state["step"] += 1
         step = state["step"]
+        gnorm_scale = self._gnorm_scale(config, grad, state, step)
         if state["state1"].dtype == torch.float:
             F.optimizer_update_32bit(self.optimizer_name, grad, p, state["state1"], config["betas"][0],
                                      config["eps"], step, config["lr"], state["state2"], config["betas"][1],
-                                     config["weight_decay"], 1.0, None, max_unorm=config["max_unorm"],
+                                     config["weight_decay"], gnorm_scale, state.get("unorm_vec"),
+                                     max_unorm=config["max_unorm"],
                                      skip_zeros=config["skip_zeros"])
         else:
             F.optimizer_update_8bit_blockwise(self.optimizer_name, grad, p, state["state1"], state["state2"],
                                               config["betas"][0], config["betas"][1], config["eps"], step,
                                               config["lr"], state["qmap1"], state["qmap2"], state["absmax1"],
-                                              state["absmax2"], config["weight_decay"], gnorm_scale=1.0,
+                                              state["absmax2"], config["weight_decay"], gnorm_scale=gnorm_scale,
                                               skip_zeros=config["skip_zeros"])
 
 
@@ -341,6 +370,7 @@ class Optimizer1State(Optimizer8bit):
             state["state1"] = torch.zeros_like(p, dtype=torch.uint8)
             state["qmap1"] = self.name2qmap["dynamic"]
             state["absmax1"] = torch.zeros((self._blocks(p),), dtype=torch.float32, device=p.device)
+        self._norm_state(config, p, state)
 
     @torch.no_grad()
     def update_step(self, group, p, gindex, pindex):
@@ -351,14 +381,16 @@ class Optimizer1State(Optimizer8bit):
         config = self.get_config(gindex, pindex, group)
         state["step"] += 1
         step = state["step"]
+        gnorm_scale = self._gnorm_scale(config, grad, state, step)
         if state["state1"].dtype == torch.float:
             F.optimizer_update_32bit(self.optimizer_name, grad, p, state["state1"], config["betas"][0],
                                      config["eps"], step, config["lr"], None, config["betas"][1],
-                                     config["weight_decay"], 1.0, None, max_unorm=config["max_unorm"],
+                                     config["weight_decay"], gnorm_scale, state.get("unorm_vec"),
+                                     max_unorm=config["max_unorm"],
                                      skip_zeros=config["skip_zeros"])
         else:
             F.optimizer_update_8bit_blockwise(self.optimizer_name, grad, p, state["state1"], None,
                                               config["betas"][0], config["betas"][1], config["eps"], step,
                                               config["lr"], state["qmap1"], None, state["absmax1"], None,
-                                              config["weight_decay"], gnorm_scale=1.0,
+                                              config["weight_decay"], gnorm_scale=gnorm_scale,
                                               skip_zeros=config["skip_zeros"])

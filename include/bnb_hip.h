@@ -403,7 +403,11 @@ int cdequantize_blockwise_nested_bf16_fp4(unsigned char* A, unsigned char* absma
 int cdequantize_blockwise_nested_bf16_nf4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
         float* offset, bnb_bf16* out, int blocksize, int blocksize2, long long n);
 /* fp32 states: ref:sycl/pythonInterface.cpp:223-241 (reference suffixes; bf16 siblings additive).
- * max_unorm > 0 is not supported (reported through cget_last_error). */
+ * max_unorm > 0 (adam, momentum, rmsprop) clips the norm of the update against max_unorm * param_norm: `unorm` then
+ * points to one float, which the call overwrites with the squared L2 norm of this step's trial update (a fixed-order
+ * fp64 reduction, no atomics; it need not be zeroed) before the update reads it on the device.  With max_unorm == 0
+ * `unorm` is not touched and may be null.  lion and adagrad report max_unorm > 0 through cget_last_error: the
+ * reference's Lion "norm" is a signed sum and its Adagrad update ignores the scale. */
 void cadam32bit_grad_fp32(float* g, float* p, float* state1, float* state2, float* unorm, float max_unorm,
         float param_norm, const float beta1, const float beta2, const float eps, const float weight_decay,
         const int step, const float lr, const float gnorm_scale, bool skip_zeros, const int n);
@@ -449,6 +453,14 @@ void clion32bit_grad_fp16(bnb_fp16* g, bnb_fp16* p, float* state1, float* state2
 void clion32bit_grad_bf16(bnb_bf16* g, bnb_bf16* p, float* state1, float* state2, float* unorm, float max_unorm,
         float param_norm, const float beta1, const float beta2, const float eps, const float weight_decay,
         const int step, const float lr, const float gnorm_scale, bool skip_zeros, const int n);
+/* percentile clipping: ref:sycl/pythonInterface.cpp:284-285.  Overwrites gnorm_vec[step % 100] (all 100 entries when
+ * step == 1) with the squared L2 norm of g: exact fp64 products summed in a fixed order and rounded once to fp32, so
+ * the same input gives the same bits on every run (the reference zeroes the entry with a blocking memset and
+ * accumulates into it with float atomics). */
+void cpercentile_clipping_g32(float* g, float* gnorm_vec, int step, const int n);
+void cpercentile_clipping_g16(bnb_fp16* g, float* gnorm_vec, int step, const int n);
+/* [additive] bf16 sibling */
+void cpercentile_clipping_gbf16(bnb_bf16* g, float* gnorm_vec, int step, const int n);
 
 /* ---- [additive] nested statistics -> fp32 absmax in one launch:
  * out[i] = code2[q[i]] * absmax2[i / blocksize2] + *offset (fp32 product, then fp32 add), the result of
