@@ -1,4 +1,5 @@
-// Optimizer updates: 8-bit blockwise states and 32-bit states, gfx950.
+// Optimizer updates: 8-bit blockwise states, 8-bit states with one global maximum per state
+// tensor, and 32-bit states, gfx950.
 //
 //   8-bit blockwise  kOptimizerStatic8bit2StateBlockwise  ref:sycl/sycl_code/kernel_quant.cpp:2715-2972
 //                    kOptimizerStatic8bit1StateBlockwise  ref:sycl/sycl_code/kernel_quant.cpp:2977-3208
@@ -6,6 +7,10 @@
 //                    C-ABI c<name>_8bit_blockwise_grad_<T> ref:sycl/pythonInterface.cpp:264-284
 //   32-bit           kOptimizer32bit2State / 1State       ref:sycl/sycl_code/kernel_quant.cpp:1614-2060
 //                    C-ABI c<name>32bit_grad_<T>          ref:sycl/pythonInterface.cpp:223-241
+//   8-bit global max kPreconditionOptimizerStatic8bit{2,1}State, kOptimizerStatic8bit{2,1}State
+//                                                         ref:sycl/sycl_code/kernel_quant.cpp:2030-2645
+//                    launcher optimizerStatic8bit         ref:sycl/sycl_code/op_quant.cpp:930-1130
+//                    C-ABI c<name>_static_8bit_grad_<T>   ref:sycl/pythonInterface.cpp:243-263
 //   norms            kPercentileClipping                  ref:sycl/sycl_code/kernel_quant.cpp:2653-2703
 //                    kPreconditionOptimizer32bit{2,1}State ref:sycl/sycl_code/kernel_quant.cpp:1500-1608, 1775-1880
 //                    C-ABI cpercentile_clipping_g<T>      ref:sycl/pythonInterface.cpp:284-285
@@ -22,7 +27,8 @@
 //     128, state2 code 0) and never stored; the reference loads past n (Q2-style, Q23);
 //   * the gradient and update norms are fixed-order fp64 sums that overwrite their destination; the
 //     reference accumulates them with float atomics (Q24) into a float it zeroes first, for unorm
-//     with std::memset on the device pointer (Q25); max_unorm is refused for Lion and Adagrad (Q26, Q27).
+//     with std::memset on the device pointer (Q25); max_unorm is refused for Lion and Adagrad (Q26, Q27);
+//   * the departures of the global-max 8-bit path (Q28-Q35) are listed above its kernels.
 // sqrt is __builtin_sqrtf, which hipcc lowers to the correctly rounded sequence (v_sqrt_f32 + two fma
 // residual checks); __fsqrt_rn lowers to the bare 1-ulp v_sqrt_f32 on ROCm 7.2.
 // The bias corrections are computed once on the host in double (the reference's pow(float, int)
@@ -455,6 +461,209 @@ k_sumsq_finish(const double* __restrict__ partials, int slots, float* __restrict
   if ((int)threadIdx.x < count) out[first + threadIdx.x] = (float)total;
 }
 
+// ---------------------------------------------------------------- 8-bit states, one global max per state
+// kPreconditionOptimizerStatic8bit{2,1}State + kOptimizerStatic8bit{2,1}State (kernel_quant.cpp:2030-2645): each state
+// tensor is quantised against one fp32 maximum.  A step is three stream-ordered launches, no atomics, no memset:
+//
+//   1. k_static8_precondition walks the tensor in the chunk and slot order of k_sumsq_partials, dequantises the old
+//      state with max[0], forms the new fp32 state values (static8_state, the function the update calls too) and
+//      keeps per thread max |s1|, max |s2| and, with max_unorm > 0, the fp64 sum of the squared update terms.  Elements
+//      at or past n give -FLT_MAX and +0.0.  Workgroup b writes slot b of the workspace: three doubles per slot, laid
+//      out as three arrays of NORM_SLOTS (sum, max1, max2; a float maximum is exact in a double).
+//   2. k_static8_finish, one workgroup: the sum in the order of k_sumsq_finish, the maxima with fmaxf; it overwrites
+//      new_max1[0], new_max2[0] and (max_unorm > 0) unorm[0].
+//   3. k_optimizer_8bit_static has the structure of the blockwise kernels (2048-element blocks, the next block's loads
+//      in flight, resident_grid); it reads max, new_max and unorm from device memory, re-quantises against new_max
+//      and stores p and the state bytes.
+//
+// The arithmetic is the reference's static kernels op for op in fp32, with the departures of DESIGN.md §2 Q28-Q35:
+// every element below n is updated, new_max is overwritten each step, the quotient is the IEEE division of requant8,
+// the precondition sees the weight-decayed state the update stores (so new_max is the exact maximum of what is
+// quantised), momentum's state takes the scaled and decayed gradient, Adam's decayed weight is not multiplied by
+// update_scale, and max_unorm is refused for RMSprop and Lion.
+template <int OPT>
+__device__ __forceinline__ void static8_state(const OptScalars& k, float g, float p, float d1, float d2, float& gs,
+                                              float& s1, float& s2) {
+  gs = __fmul_rn(k.gnorm_scale, g);
+  s2 = 0.0f;
+  if (OPT == ADAM) {
+    s1 = __fadd_rn(__fmul_rn(d1, k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), gs));
+    s2 = __fadd_rn(__fmul_rn(d2, k.beta2), __fmul_rn(__fmul_rn(__fsub_rn(1.0f, k.beta2), gs), gs));
+  } else {
+    if ((OPT == MOMENTUM || OPT == RMSPROP) && k.weight_decay > 0.0f) gs = __fadd_rn(gs, __fmul_rn(p, k.weight_decay));
+    if (OPT == MOMENTUM) s1 = (k.step == 1) ? gs : __fadd_rn(__fmul_rn(d1, k.beta1), gs);
+    else if (OPT == LION) s1 = __fadd_rn(__fmul_rn(d1, k.beta2), __fmul_rn(__fsub_rn(1.0f, k.beta2), gs));
+    else s1 = __fadd_rn(__fmul_rn(d1, k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), __fmul_rn(gs, gs)));   // RMSPROP
+  }
+}
+
+template <typename T, int OPT>
+__global__ void __launch_bounds__(OPT_THREADS)
+k_static8_precondition(const T* __restrict__ g, const T* __restrict__ p, const uint8_t* __restrict__ state1,
+                       const uint8_t* __restrict__ state2, const float* __restrict__ qmap1,
+                       const float* __restrict__ qmap2, const float* __restrict__ max1,
+                       const float* __restrict__ max2, OptScalars k, float pc1, float pc2, bool want_unorm, int n,
+                       double* __restrict__ ws) {
+  __shared__ float map1[256], map2[OPT == ADAM ? 256 : 1];
+  __shared__ double xch[4];
+  __shared__ float xm[8];
+  map1[threadIdx.x] = qmap1[threadIdx.x];
+  if (OPT == ADAM) map2[threadIdx.x] = qmap2[threadIdx.x];
+  __syncthreads();
+  const float mx1 = max1[0], mx2 = (OPT == ADAM) ? max2[0] : 0.0f;
+  // only the weight-decayed gradient of momentum and RMSprop depends on p
+  const bool need_p = (OPT == MOMENTUM || OPT == RMSPROP) && k.weight_decay > 0.0f;
+  const long long chunks = ((long long)n + NORM_CHUNK - 1) / NORM_CHUNK;
+  double acc = 0.0;
+  float m1 = -FLT_MAX, m2 = -FLT_MAX;
+  for (long long c = blockIdx.x; c < chunks; c += NORM_SLOTS) {
+    const long long i0 = c * NORM_CHUNK + (long long)threadIdx.x * OPT_NPT;
+    float gv[2][8], pv[2][8];
+    uint32_t c1[2][8], c2[2][8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {                  // both halves' loads in flight before the arithmetic
+      load8(g, i0 + h * OPT_BLOCK, n, gv[h], 0.0f);
+      load8u(state1, i0 + h * OPT_BLOCK, n, c1[h], 0x80u);
+      if (OPT == ADAM) load8u(state2, i0 + h * OPT_BLOCK, n, c2[h], 0u);
+      if (need_p) load8(p, i0 + h * OPT_BLOCK, n, pv[h], 0.0f);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bool inside = i0 + h * OPT_BLOCK + j < n;
+        const float d1 = __fmul_rn(map1[c1[h][j]], mx1);
+        const float d2 = (OPT == ADAM) ? __fmul_rn(map2[c2[h][j]], mx2) : 0.0f;
+        float gs, s1, s2;
+        static8_state<OPT>(k, gv[h][j], need_p ? pv[h][j] : 0.0f, d1, d2, gs, s1, s2);
+        m1 = fmaxf(m1, inside ? fabsf(s1) : -FLT_MAX);
+        if (OPT == ADAM) m2 = fmaxf(m2, inside ? fabsf(s2) : -FLT_MAX);
+        if ((OPT == ADAM || OPT == MOMENTUM) && want_unorm) {
+          float u = s1;                            // momentum: the state is the update (kernel_quant.cpp:2445-2446)
+          if (OPT == ADAM)                         // kernel_quant.cpp:2142-2147
+            u = __fdiv_rn(__fmul_rn(s1, pc1), __fadd_rn(__builtin_sqrtf(__fmul_rn(s2, pc2)), k.eps));
+          acc += inside ? (double)__fmul_rn(u, u) : 0.0;
+        }
+      }
+    }
+  }
+  const double total = wg_sum256(acc, xch);
+  block_max256x2(m1, m2, xm);
+  if (threadIdx.x == 0) {
+    ws[blockIdx.x] = total;
+    ws[NORM_SLOTS + blockIdx.x] = (double)m1;
+    ws[2 * NORM_SLOTS + blockIdx.x] = (double)m2;
+  }
+}
+
+// reduces the slots; new_max2 and unorm may be null (one state, max_unorm == 0)
+__global__ void __launch_bounds__(OPT_THREADS)
+k_static8_finish(const double* __restrict__ ws, int slots, float* __restrict__ new_max1, float* __restrict__ new_max2,
+                 float* __restrict__ unorm) {
+  __shared__ double xch[4];
+  __shared__ float xm[8];
+  double acc = 0.0;
+  float m1 = -FLT_MAX, m2 = -FLT_MAX;
+  for (int s = threadIdx.x; s < slots; s += OPT_THREADS) {
+    acc += ws[s];
+    m1 = fmaxf(m1, (float)ws[NORM_SLOTS + s]);
+    m2 = fmaxf(m2, (float)ws[2 * NORM_SLOTS + s]);
+  }
+  const double total = wg_sum256(acc, xch);
+  block_max256x2(m1, m2, xm);
+  if (threadIdx.x == 0) {
+    new_max1[0] = m1;
+    if (new_max2 != nullptr) new_max2[0] = m2;
+    if (unorm != nullptr) unorm[0] = (float)total;
+  }
+}
+
+// one thread's inputs of a 2048-block while in flight (Opt2InT without the per-block absmax)
+template <typename T>
+struct Static8InT {
+  float gv[8], pv[8];
+  uint2 c1, c2;
+  __device__ __forceinline__ void load(const T* __restrict__ g, const T* __restrict__ p, const uint8_t* __restrict__ s1,
+                                       const uint8_t* __restrict__ s2, long long blk, int n) {
+    const long long i0 = blk * OPT_BLOCK + (long long)threadIdx.x * OPT_NPT;
+    load8(g, i0, n, gv, 0.0f);
+    c1 = load8u_packed(s1, i0, n, 0x80u);
+    c2 = s2 ? load8u_packed(s2, i0, n, 0u) : make_uint2(0u, 0u);
+    load8(p, i0, n, pv, 0.0f);
+  }
+};
+
+// `unorm` is null when max_unorm == 0; `bound` = max_unorm * param_norm (no eps in the static kernels,
+// kernel_quant.cpp:2211-2217, 2499-2505)
+template <typename T, int OPT>
+__global__ void __launch_bounds__(OPT_THREADS)
+k_optimizer_8bit_static(T* __restrict__ p, const T* __restrict__ g, uint8_t* __restrict__ state1,
+                        uint8_t* __restrict__ state2, const float* __restrict__ qmap1, const float* __restrict__ qmap2,
+                        const float* __restrict__ max1, const float* __restrict__ max2,
+                        const float* __restrict__ new_max1, const float* __restrict__ new_max2,
+                        const float* __restrict__ unorm, float bound, OptScalars k, int n) {
+  __shared__ __attribute__((aligned(16))) OptLds<OPT == ADAM> L;
+  dynmap_stage(L.map1, qmap1);
+  if (OPT == ADAM) dynmap_stage(L.map2, qmap2);
+  __syncthreads();
+  const DynMapView code1{reinterpret_cast<const char*>(L.map1)}, code2{reinterpret_cast<const char*>(L.map2)};
+  const long long nb = (n + OPT_BLOCK - 1) / OPT_BLOCK;
+  Static8InT<T> in;                              // software pipeline, as the blockwise kernels
+  long long blk = blockIdx.x;
+  if (blk < nb) in.load(g, p, state1, state2, blk, n);
+  const float mx1 = max1[0], nm1 = new_max1[0];
+  const float mx2 = (OPT == ADAM) ? max2[0] : 0.0f, nm2 = (OPT == ADAM) ? new_max2[0] : 0.0f;
+  float update_scale = 1.0f;
+  if (unorm != nullptr) {
+    const float un = __builtin_sqrtf(unorm[0]);
+    if (un > bound) update_scale = __fdiv_rn(bound, un);
+  }
+  for (; blk < nb; blk += gridDim.x) {
+    const long long i0 = blk * OPT_BLOCK + (long long)threadIdx.x * OPT_NPT;
+    float gv[8], pv[8], s1[8], s2[8];
+    uint32_t c1[8], c2[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      gv[j] = in.gv[j];
+      pv[j] = in.pv[j];
+      c1[j] = ((j < 4 ? in.c1.x : in.c1.y) >> (8 * (j & 3))) & 0xFF;
+      c2[j] = ((j < 4 ? in.c2.x : in.c2.y) >> (8 * (j & 3))) & 0xFF;
+    }
+    if (blk + gridDim.x < nb) in.load(g, p, state1, state2, blk + gridDim.x, n);
+    T po[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float d1 = __fmul_rn(code1[c1[j]], mx1);
+      const float d2 = (OPT == ADAM) ? __fmul_rn(code2[c2[j]], mx2) : 0.0f;
+      float gs;
+      static8_state<OPT>(k, gv[j], pv[j], d1, d2, gs, s1[j], s2[j]);
+      if (OPT == ADAM) {
+        const float upd = __fmul_rn(__fmul_rn(update_scale, k.step_size),
+                                    __fdiv_rn(s1[j], __fadd_rn(__builtin_sqrtf(s2[j]), k.c2eps)));
+        po[j] = Io<T>::from_f32(__fadd_rn(pv[j], upd));
+        if (k.weight_decay > 0.0f) po[j] = Io<T>::from_f32(__fmul_rn(Io<T>::to_f32(po[j]), k.decay));
+      } else if (OPT == MOMENTUM) {
+        po[j] = Io<T>::from_f32(__fadd_rn(pv[j], __fmul_rn(__fmul_rn(-k.lr, update_scale), s1[j])));
+      } else if (OPT == LION) {                  // kernel_quant.cpp:2583-2585, 2601-2604
+        float pd = pv[j];
+        if (k.weight_decay > 0.0f) pd = Io<T>::to_f32(Io<T>::from_f32(__fmul_rn(pv[j], k.decay)));
+        const float t = __fadd_rn(__fmul_rn(d1, k.beta1), __fmul_rn(__fsub_rn(1.0f, k.beta1), gs));
+        po[j] = Io<T>::from_f32(__fsub_rn(pd, __fmul_rn(k.lr, sgnf(t))));
+      } else {                                   // RMSPROP, kernel_quant.cpp:2605-2608
+        po[j] = Io<T>::from_f32(
+            __fsub_rn(pv[j], __fdiv_rn(__fmul_rn(k.lr, gs), __fadd_rn(__builtin_sqrtf(s1[j]), k.eps))));
+      }
+    }
+    store8(p, i0, n, po);
+    requant8<true>(code1, s1, nm1, c1);
+    store8u(state1, i0, n, c1);
+    if (OPT == ADAM) {
+      requant8<false>(code2, s2, nm2, c2);
+      store8u(state2, i0, n, c2);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- 32-bit states
 // kOptimizer32bit2State / 1State; gradients are rounded to T after scaling (and after weight decay for
 // one state), as the reference keeps them in g_vals.  update_scale (kernel_quant.cpp:1635-1641,
@@ -566,9 +775,10 @@ void optimizer_8bit_blockwise(T* p, T* g, uint8_t* state1, uint8_t* state2, floa
   BNB_LAUNCH_CHECK("optimizer_8bit_blockwise");
 }
 
-// The fp64 slots of the sums of squares: one 8 KB buffer per (device, stream), allocated on first use and kept for
-// the life of the process.  A stream that is capturing a graph cannot allocate; it needs a buffer from an earlier
-// (eager) call on that stream.
+// The fp64 slots of the reductions: one 24 KB buffer per (device, stream), allocated on first use and kept for the
+// life of the process.  Three doubles per slot as three arrays of NORM_SLOTS: the sums of squares use the first, the
+// global-max 8-bit step all three (sum, max1, max2).  A stream that is capturing a graph cannot allocate; it needs a
+// buffer from an earlier (eager) call on that stream.
 static double* norm_workspace(hipStream_t stream) {
   struct Entry { int dev; hipStream_t stream; double* ptr; };
   static std::mutex mu;
@@ -586,7 +796,7 @@ static double* norm_workspace(hipStream_t stream) {
     return nullptr;
   }
   double* ptr = nullptr;
-  if (hipMalloc(&ptr, NORM_SLOTS * sizeof(double)) != hipSuccess) {
+  if (hipMalloc(&ptr, 3 * NORM_SLOTS * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
     set_error(2, "optimizer norm: workspace allocation failed");
     return nullptr;
@@ -656,6 +866,47 @@ void optimizer_32bit(T* g, T* p, float* state1, float* state2, float* unorm, flo
   BNB_LAUNCH_CHECK("optimizer_32bit");
 }
 
+// One step with a global maximum per state tensor: precondition, finish, update (see k_static8_precondition).
+template <typename T, int OPT>
+void optimizer_8bit_static(T* p, T* g, uint8_t* state1, uint8_t* state2, float* unorm, float max_unorm, float param_norm,
+                           float beta1, float beta2, float eps, int step, float lr, float* qmap1, float* qmap2,
+                           float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+                           float gnorm_scale, int n) {
+  if (n <= 0) return;
+  if (max1 == nullptr || new_max1 == nullptr || qmap1 == nullptr ||
+      (OPT == ADAM && (state2 == nullptr || qmap2 == nullptr || max2 == nullptr || new_max2 == nullptr))) {
+    set_error(1, "optimizer_static_8bit: a map or max pointer is null");
+    return;
+  }
+  const bool want_unorm = max_unorm > 0.0f;
+  if (want_unorm) {
+    if constexpr (OPT == RMSPROP || OPT == LION) {
+      set_error(1, "optimizer_static_8bit: max_unorm > 0 is refused for rmsprop and lion (the reference's "
+                   "precondition accumulates no update norm for them and its update would read a stale one)");
+      return;
+    }
+    if (unorm == nullptr) { set_error(1, "optimizer_static_8bit: max_unorm > 0 needs unorm (one float)"); return; }
+  }
+  const OptScalars k = make_scalars(beta1, beta2, eps, step, lr, weight_decay, gnorm_scale, false);
+  const hipStream_t stream = current_stream();
+  double* ws = norm_workspace(stream);
+  if (ws == nullptr) return;
+  // 1.0f / (1.0f - pow(beta, step)), as NormScalars (kernel_quant.cpp:2142-2143)
+  const float pc1 = (float)(1.0 / (1.0 - std::pow((double)beta1, (double)step)));
+  const float pc2 = (float)(1.0 / (1.0 - std::pow((double)beta2, (double)step)));
+  const int slots = (int)std::min<long long>(((long long)n + NORM_CHUNK - 1) / NORM_CHUNK, NORM_SLOTS);
+  float* nm2 = (OPT == ADAM) ? new_max2 : nullptr;
+  hipLaunchKernelGGL((k_static8_precondition<T, OPT>), dim3(slots), dim3(OPT_THREADS), 0, stream, g, p, state1, state2,
+                     qmap1, qmap2, max1, max2, k, pc1, pc2, want_unorm, n, ws);
+  hipLaunchKernelGGL(k_static8_finish, dim3(1), dim3(OPT_THREADS), 0, stream, ws, slots, new_max1, nm2,
+                     want_unorm ? unorm : nullptr);
+  const long long nb = (n + OPT_BLOCK - 1) / OPT_BLOCK;
+  const auto kern = k_optimizer_8bit_static<T, OPT>;
+  hipLaunchKernelGGL(kern, dim3(resident_grid(kern, nb)), dim3(OPT_THREADS), 0, stream, p, g, state1, state2, qmap1,
+                     qmap2, max1, max2, new_max1, nm2, want_unorm ? unorm : nullptr, max_unorm * param_norm, k, n);
+  BNB_LAUNCH_CHECK("optimizer_static_8bit");
+}
+
 }  // namespace bnb
 
 using namespace bnb;
@@ -687,6 +938,31 @@ BNB_BLOCKWISE8(adagrad, ADAGRAD, bf16_t, bf16)
 BNB_BLOCKWISE8(lion, LION, float, fp32)
 BNB_BLOCKWISE8(lion, LION, fp16_t, fp16)
 BNB_BLOCKWISE8(lion, LION, bf16_t, bf16)
+
+#define BNB_STATIC8(fname, OPT, gtype, gbits)                                                                      \
+  void c##fname##_static_8bit_grad_##gbits(gtype* p, gtype* g, unsigned char* state1, unsigned char* state2,         \
+                                           float* unorm, float max_unorm, float param_norm, float beta1, float beta2, \
+                                           float eps, int step, float lr, float* quantiles1, float* quantiles2,      \
+                                           float* max1, float* max2, float* new_max1, float* new_max2,               \
+                                           float weight_decay, float gnorm_scale, int n) {                           \
+    BNB_RANGE("c" #fname "_static_8bit_grad_" #gbits);                                                             \
+    optimizer_8bit_static<gtype, OPT>(p, g, state1, state2, unorm, max_unorm, param_norm, beta1, beta2, eps, step,   \
+                                      lr, quantiles1, quantiles2, max1, max2, new_max1, new_max2, weight_decay,      \
+                                      gnorm_scale, n);                                                               \
+  }
+// ref:sycl/pythonInterface.cpp:243-262 + the bf16 siblings (additive)
+BNB_STATIC8(adam, ADAM, float, 32)
+BNB_STATIC8(adam, ADAM, fp16_t, 16)
+BNB_STATIC8(adam, ADAM, bf16_t, bf16)
+BNB_STATIC8(momentum, MOMENTUM, float, 32)
+BNB_STATIC8(momentum, MOMENTUM, fp16_t, 16)
+BNB_STATIC8(momentum, MOMENTUM, bf16_t, bf16)
+BNB_STATIC8(rmsprop, RMSPROP, float, 32)
+BNB_STATIC8(rmsprop, RMSPROP, fp16_t, 16)
+BNB_STATIC8(rmsprop, RMSPROP, bf16_t, bf16)
+BNB_STATIC8(lion, LION, float, 32)
+BNB_STATIC8(lion, LION, fp16_t, 16)
+BNB_STATIC8(lion, LION, bf16_t, bf16)
 
 #define BNB_FUNC32(fname, OPT, gtype, gbits)                                                                    \
   void c##fname##32bit_grad_##gbits(gtype* g, gtype* p, float* state1, float* state2, float* unorm,             \

@@ -393,6 +393,27 @@ __global__ void k_dequantize_cpu_semantics(const float* __restrict__ code, const
     out[i] = __fmul_rn(s_code[A[i]], absmax[i / blocksize]);
 }
 
+// ============================================================================ whole-tensor 8-bit codec
+// kQuantize / kDequantize (ref:sycl/sycl_code/kernel_quant.cpp, C-ABI pythonInterface.cpp:196-197): one map for the
+// whole tensor, no absmax; the caller scales.  fp32 only, as the reference.
+__global__ void __launch_bounds__(256)
+k_quantize_map(const float* __restrict__ code, const float* __restrict__ A, uint8_t* __restrict__ out, long long n) {
+  __shared__ float s_code[256];
+  s_code[threadIdx.x] = code[threadIdx.x];
+  __syncthreads();
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    out[i] = (uint8_t)quantize_dynamic8((const float*)s_code, A[i]);
+}
+
+__global__ void __launch_bounds__(256)
+k_dequantize_map(const float* __restrict__ code, const uint8_t* __restrict__ A, float* __restrict__ out, long long n) {
+  __shared__ float s_code[256];
+  s_code[threadIdx.x] = code[threadIdx.x];
+  __syncthreads();
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    out[i] = s_code[A[i]];
+}
+
 // ============================================================================ launchers
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -611,6 +632,23 @@ BNB_DEQUANT_NESTED_ABI(cdequantize_blockwise_nested_fp16_fp4, fp16_t, FP4)
 BNB_DEQUANT_NESTED_ABI(cdequantize_blockwise_nested_fp16_nf4, fp16_t, NF4)
 BNB_DEQUANT_NESTED_ABI(cdequantize_blockwise_nested_bf16_fp4, bf16_t, FP4)
 BNB_DEQUANT_NESTED_ABI(cdequantize_blockwise_nested_bf16_nf4, bf16_t, NF4)
+
+// whole-tensor codec, ref:sycl/pythonInterface.cpp:196-197
+void cquantize(float* code, float* A, unsigned char* out, int n) {
+  BNB_RANGE("cquantize");
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_quantize_map, dim3(stream_grid(n, 256)), dim3(256), 0, current_stream(), code, A, out,
+                     (long long)n);
+  BNB_LAUNCH_CHECK("quantize");
+}
+
+void cdequantize(float* code, unsigned char* A, float* out, int n) {
+  BNB_RANGE("cdequantize");
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_dequantize_map, dim3(stream_grid(n, 256)), dim3(256), 0, current_stream(), code, A, out,
+                     (long long)n);
+  BNB_LAUNCH_CHECK("dequantize");
+}
 
 // The host-pointer entry points cquantize_blockwise_cpu_fp32 / cdequantize_blockwise_cpu_fp32
 // (ref:sycl/pythonInterface.cpp:419-420) run on the host cores: cpu_ops.cpp.

@@ -415,6 +415,63 @@ def dequantize_blockwise(A: Tensor, quant_state: Optional[QuantState] = None, ab
     return out
 
 
+# ----------------------------------------------------------------------------- whole-tensor 8-bit codec
+def quantize(A: Tensor, code: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tuple[Tensor, Tuple[Tensor, Tensor]]:
+    """8-bit codes of A / max|A| on one map for the whole tensor (ref:functional.py:1427-1443); returns
+    (codes, (absmax, code))."""
+    if code is None:
+        code = _dynamic_map(A.device)
+    absmax = torch.abs(A).max()
+    if absmax.dtype != torch.float32:
+        absmax = absmax.float()
+    inp = A / absmax
+    out = quantize_no_absmax(inp, code, out)
+    return out, (absmax, code)
+
+
+def dequantize(A: Tensor, state: Optional[Tuple[Tensor, Tensor]] = None, absmax: Optional[Tensor] = None,
+               code: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """ref:functional.py:1446-1463: code[A] * absmax."""
+    assert state is not None or absmax is not None
+    if code is None and state is None:
+        code = _dynamic_map(A.device)
+    if state is None:
+        state = (absmax, code)
+    out = dequantize_no_absmax(A, state[1], out)
+    return out * state[0]
+
+
+def quantize_no_absmax(A: Tensor, code: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The nearest entry of the 256-entry map `code` for every element of the fp32 tensor A, as uint8
+    (ref:functional.py:1466-1493 -> cquantize: the dynamic-map binary search with midpoint rounding)."""
+    if A.dtype != torch.float32:
+        raise ValueError(f"quantize_no_absmax takes fp32 input, got {A.dtype}")
+    if out is None:
+        out = torch.zeros_like(A, dtype=torch.uint8)
+    code = code.to(A.device)
+    is_on_gpu([code, A, out])
+    prev_device = pre_call(A.device)
+    Ac = A.contiguous()
+    lib.cquantize(get_ptr(code), get_ptr(Ac), get_ptr(out), ct.c_int(A.numel()))
+    post_call(prev_device)
+    return out
+
+
+def dequantize_no_absmax(A: Tensor, code: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """code[A] as fp32 (ref:functional.py:1496-1523 -> cdequantize)."""
+    if A.dtype != torch.uint8:
+        raise ValueError(f"dequantize_no_absmax takes uint8 codes, got {A.dtype}")
+    if out is None:
+        out = torch.zeros_like(A, dtype=torch.float32)
+    code = code.to(A.device)
+    is_on_gpu([code, A, out])
+    prev_device = pre_call(A.device)
+    Ac = A.contiguous()
+    lib.cdequantize(get_ptr(code), get_ptr(Ac), get_ptr(out), ct.c_int(A.numel()))
+    post_call(prev_device)
+    return out
+
+
 # ----------------------------------------------------------------------------- 4-bit
 def quantize_fp4(A, absmax=None, out=None, blocksize=64, compress_statistics=False, quant_storage=torch.uint8):
     return quantize_4bit(A, absmax, out, blocksize, compress_statistics, "fp4", quant_storage)
@@ -1717,6 +1774,48 @@ def optimizer_update_8bit_blockwise(optimizer_name: str, g: Tensor, p: Tensor, s
                ct.c_float(eps), ct.c_int32(step), ct.c_float(lr), get_ptr(qmap1), get_ptr(qmap2), get_ptr(absmax1),
                get_ptr(absmax2), ct.c_float(weight_decay), ct.c_float(gnorm_scale), ct.c_bool(skip_zeros),
                ct.c_int32(g.numel()))
+    post_call(prev_device)
+
+
+# optimizers with a global-max 8-bit kernel (ref:sycl/pythonInterface.cpp:256-263) and, of those, the ones whose
+# max_unorm the backend refuses
+_STATIC8_NAMES = ("adam", "momentum", "rmsprop", "lion")
+_NO_UNORM_STATIC8 = {name: "the reference's precondition accumulates no update norm for it and its update would read "
+                           "a stale one" for name in ("rmsprop", "lion")}
+
+
+def optimizer_update_8bit(optimizer_name: str, g: Tensor, p: Tensor, state1: Tensor, state2: Optional[torch.Tensor],
+                          beta1: float, beta2: float, eps: float, step: int, lr: float, qmap1: Tensor,
+                          qmap2: Optional[torch.Tensor], max1: Tensor, max2: Optional[torch.Tensor], new_max1: Tensor,
+                          new_max2: Optional[torch.Tensor], weight_decay: float = 0.0, gnorm_scale: float = 1.0,
+                          unorm_vec: Optional[torch.Tensor] = None, max_unorm: float = 0.0) -> None:
+    """In-place optimizer step with 8-bit states quantised against one global maximum per state tensor
+    (ref:functional.py:1621-1751 -> c<name>_static_8bit_grad_<T>; "lamb" runs the Adam kernels).
+
+    state = qmap[code] * max[0].  The call overwrites new_max1[0] / new_max2[0] with the exact maxima of the new
+    state values (a fixed-order reduction on the device; they need not be zeroed) and stores the codes against
+    them, so the caller swaps max and new_max afterwards, as the optimizer classes do.  max_unorm > 0 (adam /
+    lamb and momentum) clips the L2 norm of the update against max_unorm * ||p|| and leaves its square in
+    unorm_vec[0].  fp32, fp16 and bf16 gradients; there is no CPU implementation of this path."""
+    name = "adam" if optimizer_name == "lamb" else optimizer_name
+    param_norm = 0.0
+    if max_unorm > 0.0:
+        if name in _NO_UNORM_STATIC8:
+            raise NotImplementedError(f"max_unorm > 0 is not supported for {optimizer_name} with 8-bit state: "
+                                      f"{_NO_UNORM_STATIC8[name]}")
+        if unorm_vec is None:
+            raise ValueError("max_unorm > 0 needs unorm_vec (one fp32 element on the gradient's device)")
+        param_norm = torch.norm(p.data.float()).item()
+    if name not in _STATIC8_NAMES or g.dtype not in _DTYPE_INDEX or state1.dtype != torch.uint8:
+        raise ValueError(f"Gradient+optimizer bit data type combination not supported: grad {g.dtype}, "
+                         f"optimizer {optimizer_name} with state {state1.dtype}")
+    optim_func = getattr(lib, f"c{name}_static_8bit_grad_{('32', '16', 'bf16')[_DTYPE_INDEX[g.dtype]]}")
+    is_on_gpu([g, p, state1, state2, unorm_vec, qmap1, qmap2, max1, max2, new_max1, new_max2])
+    prev_device = pre_call(g.device)
+    optim_func(get_ptr(p), get_ptr(g), get_ptr(state1), get_ptr(state2), get_ptr(unorm_vec), ct.c_float(max_unorm),
+               ct.c_float(param_norm), ct.c_float(beta1), ct.c_float(beta2), ct.c_float(eps), ct.c_int32(step),
+               ct.c_float(lr), get_ptr(qmap1), get_ptr(qmap2), get_ptr(max1), get_ptr(max2), get_ptr(new_max1),
+               get_ptr(new_max2), ct.c_float(weight_decay), ct.c_float(gnorm_scale), ct.c_int32(g.numel()))
     post_call(prev_device)
 
 

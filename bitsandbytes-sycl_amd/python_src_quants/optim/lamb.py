@@ -1,11 +1,13 @@
-"""LAMB with fp32 states, ref:python_src_quants/optim/lamb.py (kernel "lamb": the Adam entry points with the
-update's L2 norm clipped against max_unorm * ||p||).
+"""LAMB, ref:python_src_quants/optim/lamb.py (kernel "lamb": the Adam entry points with the update's L2 norm
+clipped against max_unorm * ||p||), with fp32 states or, in LAMB8bit, 8-bit states.
 
 The reference's three classes accept ``max_unorm`` and then pass the literal 1.0 to the base class
 (ref:optim/lamb.py:71, 135, 199), so the argument has no effect there; here it is honoured (the default,
 1.0, gives the reference's behaviour).  ``bias_correction`` and ``adam_w_mode`` are accepted and unused, as
-in the reference.  LAMB8bit keeps the reference's ``block_wise=False`` default and therefore ends in the
-refusal of non-blockwise 8-bit state for parameters of at least ``min_8bit_size`` elements.
+in the reference.  LAMB8bit keeps the reference's ``block_wise=False`` default: parameters of at least
+``min_8bit_size`` elements keep 8-bit states quantised against one global maximum per state tensor
+(F.optimizer_update_8bit), the one 8-bit state kind that takes ``max_unorm``.  That path runs on a GPU only; a
+parameter that is not on one is refused.
 """
 from .optimizer import Optimizer2State
 

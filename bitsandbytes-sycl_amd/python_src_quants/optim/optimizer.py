@@ -1,21 +1,28 @@
 """8-bit / 32-bit state optimizers, mirroring ref:python_src_quants/optim/optimizer.py.
 
 Optimizer8bit / Optimizer2State / Optimizer1State keep the reference's constructor arguments, state
-keys (step, state1, state2, qmap1, qmap2, absmax1, absmax2, gnorm_vec, unorm_vec), GlobalOptimManager
-overrides and state_dict round trip.  Per parameter the update is one HIP launch:
-  * 8-bit blockwise states (optim_bits=8, block_wise=True, numel >= min_8bit_size):
+keys (step, state1, state2, qmap1, qmap2, absmax1, absmax2, max1, max2, new_max1, new_max2, gnorm_vec,
+unorm_vec), GlobalOptimManager overrides and state_dict round trip.  Per parameter the update is:
+  * 8-bit blockwise states (optim_bits=8, block_wise=True, numel >= min_8bit_size), one HIP launch:
     F.optimizer_update_8bit_blockwise -> c<name>_8bit_blockwise_grad_<T>;
-  * fp32 states otherwise: F.optimizer_update_32bit -> c<name>32bit_grad_<T>.
+  * 8-bit states with one global maximum per state tensor (optim_bits=8, block_wise=False, numel >=
+    min_8bit_size; adam / lamb, momentum, rmsprop, lion), three stream-ordered launches:
+    F.optimizer_update_8bit -> c<name>_static_8bit_grad_<T>.  state["max1"] / state["max2"] scale the stored
+    codes, the call writes state["new_max1"] / state["new_max2"], and the two are swapped after it;
+  * fp32 states otherwise, one launch: F.optimizer_update_32bit -> c<name>32bit_grad_<T>.
 Two settings put a full-tensor L2 norm (a fixed-order reduction on the device, equal bits for equal
 inputs) ahead of it:
   * percentile_clipping < 100 (both state kinds): F.percentile_clipping records the gradient's squared
     norm in state["gnorm_vec"] (the last 100) and the update scales the gradient by its gnorm_scale;
-  * max_unorm > 0 (fp32 states; adam / lamb, momentum, rmsprop): the update's norm is clipped against
-    max_unorm * ||p||; its square is left in state["unorm_vec"].
-Not provided by this backend (they raise NotImplementedError): the non-blockwise 8-bit path
-(global max, kOptimizerStatic8bit2State), paged state, max_unorm with 8-bit blockwise state (the
-reference's blockwise kernel has no such input and drops the setting) and max_unorm for lion and
-adagrad (the reference's Lion norm is a signed sum, its Adagrad update ignores the scale).
+  * max_unorm > 0 (fp32 states: adam / lamb, momentum, rmsprop; global-max 8-bit states: adam / lamb,
+    momentum): the update's norm is clipped against max_unorm * ||p||; its square is left in
+    state["unorm_vec"].
+Not provided by this backend (they raise NotImplementedError): the non-blockwise 8-bit path for a
+parameter that is not on a GPU (there is no CPU implementation of it) and for adagrad (the reference has
+no such kernel), paged state, max_unorm with 8-bit blockwise state (the reference's blockwise kernel has
+no such input and drops the setting), max_unorm for lion and adagrad (the reference's Lion norm is a
+signed sum, its Adagrad update ignores the scale) and, with global-max 8-bit state, for rmsprop (the
+reference's precondition accumulates no norm for it).
 """
 from __future__ import annotations
 
@@ -229,10 +236,20 @@ class Optimizer8bit(torch.optim.Optimizer):
         if p.numel() < config["min_8bit_size"]:
             dtype = torch.float32
         if dtype == torch.uint8 and not config["block_wise"]:
-            raise NotImplementedError("non-blockwise 8-bit optimizer state is not supported by the MI355X backend "
-                                      "(use block_wise=True)")
+            # the global-max path has no CPU implementation: a parameter that is not on a GPU is refused
+            if not p.is_cuda:
+                raise NotImplementedError("non-blockwise 8-bit optimizer state is not supported by the MI355X backend "
+                                          "(use block_wise=True)")
+            if self.optimizer_name not in ("lamb",) + F._STATIC8_NAMES:
+                raise NotImplementedError(f"non-blockwise 8-bit optimizer state is not supported for "
+                                          f"{self.optimizer_name} (the reference has no such kernel; use "
+                                          f"block_wise=True)")
         if config["max_unorm"] > 0.0:
-            if dtype == torch.uint8:
+            if dtype == torch.uint8 and not config["block_wise"]:
+                if self.optimizer_name in F._NO_UNORM_STATIC8:
+                    raise NotImplementedError(f"max_unorm > 0 is not supported for {self.optimizer_name} with 8-bit "
+                                              f"state: {F._NO_UNORM_STATIC8[self.optimizer_name]}")
+            elif dtype == torch.uint8:
                 raise NotImplementedError("max_unorm > 0 with 8-bit blockwise state is not supported by the MI355X "
                                           "backend (the reference's blockwise kernel has no such input and would "
                                           "drop the setting)")
@@ -315,9 +332,13 @@ class Optimizer2State(Optimizer8bit):
             state["qmap1"] = self.name2qmap["dynamic"]
             state["state2"] = torch.zeros_like(p, dtype=torch.uint8)
             state["qmap2"] = self.name2qmap["udynamic"]
-            blocks = self._blocks(p)
-            state["absmax1"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
-            state["absmax2"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
+            if config["block_wise"]:
+                blocks = self._blocks(p)
+                state["absmax1"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
+                state["absmax2"] = torch.zeros((blocks,), dtype=torch.float32, device=p.device)
+            else:
+                for key in ("max1", "new_max1", "max2", "new_max2"):
+                    state[key] = torch.zeros((1,), dtype=torch.float32, device=p.device)
         self._norm_state(config, p, state)
 
     @torch.no_grad()
@@ -336,6 +357,14 @@ class Optimizer2State(Optimizer8bit):
                                      config["weight_decay"], gnorm_scale, state.get("unorm_vec"),
                                      max_unorm=config["max_unorm"],
                                      skip_zeros=config["skip_zeros"])
+        elif "max1" in state:                    # global-max 8-bit state (init_state: block_wise=False)
+            F.optimizer_update_8bit(self.optimizer_name, grad, p, state["state1"], state["state2"],
+                                    config["betas"][0], config["betas"][1], config["eps"], step, config["lr"],
+                                    state["qmap1"], state["qmap2"], state["max1"], state["max2"], state["new_max1"],
+                                    state["new_max2"], config["weight_decay"], gnorm_scale=gnorm_scale,
+                                    unorm_vec=state.get("unorm_vec"), max_unorm=config["max_unorm"])
+            state["max1"], state["new_max1"] = state["new_max1"], state["max1"]
+            state["max2"], state["new_max2"] = state["new_max2"], state["max2"]
         else:
             F.optimizer_update_8bit_blockwise(self.optimizer_name, grad, p, state["state1"], state["state2"],
                                               config["betas"][0], config["betas"][1], config["eps"], step,
@@ -369,7 +398,11 @@ class Optimizer1State(Optimizer8bit):
             self._qmaps(p)
             state["state1"] = torch.zeros_like(p, dtype=torch.uint8)
             state["qmap1"] = self.name2qmap["dynamic"]
-            state["absmax1"] = torch.zeros((self._blocks(p),), dtype=torch.float32, device=p.device)
+            if config["block_wise"]:
+                state["absmax1"] = torch.zeros((self._blocks(p),), dtype=torch.float32, device=p.device)
+            else:
+                state["max1"] = torch.zeros((1,), dtype=torch.float32, device=p.device)
+                state["new_max1"] = torch.zeros((1,), dtype=torch.float32, device=p.device)
         self._norm_state(config, p, state)
 
     @torch.no_grad()
@@ -388,6 +421,13 @@ class Optimizer1State(Optimizer8bit):
                                      config["weight_decay"], gnorm_scale, state.get("unorm_vec"),
                                      max_unorm=config["max_unorm"],
                                      skip_zeros=config["skip_zeros"])
+        elif "max1" in state:                    # global-max 8-bit state (init_state: block_wise=False)
+            F.optimizer_update_8bit(self.optimizer_name, grad, p, state["state1"], None, config["betas"][0],
+                                    config["betas"][1], config["eps"], step, config["lr"], state["qmap1"], None,
+                                    state["max1"], None, state["new_max1"], None, config["weight_decay"],
+                                    gnorm_scale=gnorm_scale, unorm_vec=state.get("unorm_vec"),
+                                    max_unorm=config["max_unorm"])
+            state["max1"], state["new_max1"] = state["new_max1"], state["max1"]
         else:
             F.optimizer_update_8bit_blockwise(self.optimizer_name, grad, p, state["state1"], None,
                                               config["betas"][0], config["betas"][1], config["eps"], step,

@@ -54,6 +54,12 @@ void cdequantize_blockwise_bf16(float* code, unsigned char* A, float* absmax, bn
 void cdequantize_blockwise_bf16_fp4(float* code, unsigned char* A, float* absmax, bnb_bf16* out, int blocksize, const int n); /* :220 */
 void cdequantize_blockwise_bf16_nf4(float* code, unsigned char* A, float* absmax, bnb_bf16* out, int blocksize, const int n); /* :221 */
 
+/* ---- whole-tensor 8-bit codec: ref:sycl/pythonInterface.cpp:196-197 (fp32 only, as the reference) ----
+ * cquantize: out[i] = dQuantize<0>(code, A[i]) on the given 256-entry map (binary search + midpoint rounding; the
+ * caller scales A into the map's range).  cdequantize: out[i] = code[A[i]]. */
+void cquantize(float* code, float* A, unsigned char* out, int n);
+void cdequantize(float* code, unsigned char* A, float* out, int n);
+
 /* ---- host-pointer CPU-path entry points: ref:sycl/pythonInterface.cpp:419-420 (cpu_ops.cpp semantics:
  * division A/absmax, nearest code with ties to the left, code[0] := -1 in place).  Run on the host cores
  * (csrc/cpu_ops.cpp; no HIP call, so they work without a GPU), synchronous on return. */
@@ -453,6 +459,62 @@ void clion32bit_grad_fp16(bnb_fp16* g, bnb_fp16* p, float* state1, float* state2
 void clion32bit_grad_bf16(bnb_bf16* g, bnb_bf16* p, float* state1, float* state2, float* unorm, float max_unorm,
         float param_norm, const float beta1, const float beta2, const float eps, const float weight_decay,
         const int step, const float lr, const float gnorm_scale, bool skip_zeros, const int n);
+/* 8-bit states with one global maximum per state tensor: ref:sycl/pythonInterface.cpp:243-263 (bf16 siblings
+ * additive).  state = code[q] * max[0].  One call is three stream-ordered launches (no atomics, nothing to zero): a
+ * precondition pass forms the new state values and reduces max|s1|, max|s2| and, with max_unorm > 0, the squared L2 norm
+ * of the update in a fixed order; a finishing launch overwrites new_max1[0], new_max2[0] and unorm[0]; the update
+ * re-quantises against new_max and stores p and the state bytes.  The caller swaps max and new_max after the call.
+ * Adam uses both states; the others take state2 = quantiles2 = max2 = new_max2 = NULL.  With max_unorm == 0 `unorm`
+ * is not touched and may be null.  rmsprop and lion report max_unorm > 0 through cget_last_error.  Departures from
+ * the reference's kernels: DESIGN.md section 2, Q28-Q35. */
+void cadam_static_8bit_grad_32(float* p, float* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void cadam_static_8bit_grad_16(bnb_fp16* p, bnb_fp16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void cadam_static_8bit_grad_bf16(bnb_bf16* p, bnb_bf16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void cmomentum_static_8bit_grad_32(float* p, float* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void cmomentum_static_8bit_grad_16(bnb_fp16* p, bnb_fp16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void cmomentum_static_8bit_grad_bf16(bnb_bf16* p, bnb_bf16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void crmsprop_static_8bit_grad_32(float* p, float* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void crmsprop_static_8bit_grad_16(bnb_fp16* p, bnb_fp16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void crmsprop_static_8bit_grad_bf16(bnb_bf16* p, bnb_bf16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void clion_static_8bit_grad_32(float* p, float* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void clion_static_8bit_grad_16(bnb_fp16* p, bnb_fp16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
+void clion_static_8bit_grad_bf16(bnb_bf16* p, bnb_bf16* g, unsigned char* state1, unsigned char* state2, float* unorm,
+        float max_unorm, float param_norm, float beta1, float beta2, float eps, int step, float lr, float* quantiles1,
+        float* quantiles2, float* max1, float* max2, float* new_max1, float* new_max2, float weight_decay,
+        float gnorm_scale, int n);
 /* percentile clipping: ref:sycl/pythonInterface.cpp:284-285.  Overwrites gnorm_vec[step % 100] (all 100 entries when
  * step == 1) with the squared L2 norm of g: exact fp64 products summed in a fixed order and rounded once to fp32, so
  * the same input gives the same bits on every run (the reference zeroes the entry with a blocking memset and
