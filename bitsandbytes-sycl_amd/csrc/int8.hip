@@ -809,6 +809,38 @@ int cigemm_row_i32_ws(int m, int n, int k, const int8_t* A, const int8_t* B, int
 }
 long long cigemmlt_workspace_bytes(int m, int n, int k) { return igemm_workspace_bytes(m, n, k); }
 
+// ref:sycl/pythonInterface.cpp:289-293 -> gemmex / strided_gemmex op_gemm.cpp:263-301: BLAS column-major
+// C(m x n, ldc) = op(A)(m x k) . op(B)(k x n), int8 in, int32 out, alpha 1, beta 0.  Seen row-major, C is
+// Out[j][i] = sum_k X(j, k) Y(i, k) with X = op(B)^T (K-contiguous unless transposeB) and Y = op(A) (K-contiguous
+// when transposeA).  The context is not used.
+void cigemm(void* context, bool transposeA, bool transposeB, int m, int n, int k, void* A, void* B, void* C, int lda,
+            int ldb, int ldc) {
+  BNB_RANGE("cigemm");
+  (void)context;
+  if (m <= 0 || n <= 0 || k <= 0) return;
+  // both K-contiguous and 16-B aligned (what the row-major kernels load by): the existing route -- the 256 x 256
+  // kernel from 256 x 256 outputs with k % 128 == 0, else the 128 x 128 k_igemm.  No workspace is passed (the call
+  // must not allocate), so that route's split-K is never taken here; cigemm_row_i32_ws is the entry point with it.
+  // Everything else runs on igemm_strided.hip
+  if (transposeA && !transposeB && (((uintptr_t)A | (uintptr_t)B | (uintptr_t)lda | (uintptr_t)ldb) & 15) == 0) {
+    if (lda < k || ldb < k || ldc < m) {
+      set_error((int)hipErrorInvalidValue, "igemm: leading dimension smaller than the matrix extent");
+      return;
+    }
+    launch_igemm<ROW, ROW, EPI_I32_ROW>(n, m, k, (const int8_t*)B, (const int8_t*)A, C, nullptr, ldb, lda, ldc);
+    return;
+  }
+  launch_igemm_strided(transposeB, !transposeA, n, m, k, (const int8_t*)B, (const int8_t*)A, (int32_t*)C, ldb, lda, ldc,
+                       0, 0, 0, 1);
+}
+void cbatched_igemm(void* context, bool transposeA, bool transposeB, int m, int n, int k, void* A, void* B, void* C,
+                    int lda, int ldb, int ldc, long strideA, long strideB, long strideC, int batchCount) {
+  BNB_RANGE("cbatched_igemm");
+  (void)context;
+  launch_igemm_strided(transposeB, !transposeA, n, m, k, (const int8_t*)B, (const int8_t*)A, (int32_t*)C, ldb, lda, ldc,
+                       strideB, strideA, strideC, batchCount);
+}
+
 void cdequant_mm_int32_fp16(int* A, float* rowStats, float* colStats, fp16_t* out, float* newRowStats,
                             float* newcolStats, fp16_t* bias, int numRows, int numCols) {
   BNB_RANGE("cdequant_mm_int32_fp16");

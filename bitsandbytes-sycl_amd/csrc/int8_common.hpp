@@ -56,5 +56,12 @@ int igemm_4wave(int m, int n, int k, const int8_t* A, long long lda, const int8_
                 long long ldc, bool dequant, const float* rowStats, const float* colStats, const fp16_t* bias);
 long long hgemm_tiles(int m, int n);
 long long igemm_workspace_bytes(int m, int n, int k);
+// batched int8 product with K-contiguous or K-strided operands (igemm_strided.hip):
+// Out[b][r][c] = sum_k X_b(r, k) * Y_b(c, k), X has R rows, Y has Cn rows; a K-contiguous operand has (r, k) at
+// P[r * ld + k], a K-strided one at P[k * ld + r]; sx / sy / sc are the batch strides.  0 = launched (or nothing to
+// do), 1 = error (recorded with set_error)
+int launch_igemm_strided(bool x_kstrided, bool y_kstrided, int R, int Cn, int K, const int8_t* X, const int8_t* Y,
+                         int32_t* Out, long long ldx, long long ldy, long long ldc, long long sx, long long sy,
+                         long long sc, int batch);
 
 }  // namespace bnb

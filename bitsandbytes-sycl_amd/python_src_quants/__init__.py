@@ -5,10 +5,11 @@ Drop-in for ref:python_src_quants/__init__.py on the hot path: `functional`, `nn
 `libbitsandbytes_hip.so` built from ../csrc.
 """
 from . import functional, nn, optim, utils
-from .autograd._functions import MatmulLtState, MatMul4Bit, MatMul8bitLt, matmul, matmul_4bit
+from .autograd._functions import (MatmulLtState, MatMul4Bit, MatMul8bit, MatMul8bitLt, bmm_cublas, matmul, matmul_4bit,
+                                  matmul_cublas, mm_cublas)
 from .cextension import HIP_AVAILABLE, lib
 
 __version__ = "0.43.2.mi355x0"
 
 __all__ = ["functional", "nn", "optim", "utils", "matmul", "matmul_4bit", "MatmulLtState", "MatMul4Bit", "MatMul8bitLt",
-           "lib", "HIP_AVAILABLE"]
+           "MatMul8bit", "mm_cublas", "bmm_cublas", "matmul_cublas", "lib", "HIP_AVAILABLE"]

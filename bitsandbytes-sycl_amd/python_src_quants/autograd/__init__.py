@@ -1,1 +1,2 @@
-from ._functions import MatmulLtState, MatMul4Bit, MatMul8bitLt, matmul, matmul_4bit  # noqa: F401
+from ._functions import (MatmulLtState, MatMul4Bit, MatMul8bit, MatMul8bitLt, bmm_cublas, matmul,  # noqa: F401
+                         matmul_4bit, matmul_cublas, mm_cublas)

@@ -214,6 +214,76 @@ class MatMul8bitLt(torch.autograd.Function):
         return grad_A, grad_B, None, grad_bias, None
 
 
+# ----------------------------------------------------------------------------- vector-wise 8-bit
+def _swap_last_two(t: torch.Tensor) -> torch.Tensor:
+    return t.permute(0, 2, 1) if t.dim() == 3 else t.permute(1, 0)
+
+
+class MatMul8bit(torch.autograd.Function):
+    """Vector-wise quantised matmul (ref:autograd/_functions.py:107-210): both operands go to int8 with one scale per
+    vector along the contraction (F.vectorwise_quant), the product is the exact int8 GEMM F.igemm -- transposed
+    views read in place by the K-strided kernel -- and F.vectorwise_mm_dequant scales it back.  `precision` holds the
+    bits of the forward, grad_B and grad_A products; any entry other than 8 runs that product as torch.matmul."""
+
+    @staticmethod
+    def forward(ctx, A, B, out=None, quant_type="vector", precision=None):
+        if precision is None:
+            precision = [8, 8, 8]
+        if precision[0] != 8:
+            with torch.no_grad():
+                output = torch.matmul(A, B)
+        else:
+            qA, SA = F.vectorwise_quant(A, dim=-1, quant_type=quant_type)
+            qB, SB = F.vectorwise_quant(B, dim=0 if B.dim() == 2 else 1, quant_type=quant_type)
+            output = F.vectorwise_mm_dequant(F.igemm(qA, qB), SA, SB, A.dtype, quant_type)
+        if A.requires_grad or B.requires_grad:
+            ctx.save_for_backward(A, B)
+        ctx.quant_type = quant_type
+        ctx.precision = precision
+        return output
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        A, B = ctx.saved_tensors
+        quant_type, precision = ctx.quant_type, ctx.precision
+        grad_A = grad_B = None
+
+        if B.requires_grad:
+            if precision[1] != 8:
+                with torch.no_grad():
+                    grad_B = torch.matmul(_swap_last_two(A), grad_output)
+            elif B.dim() == 2 and A.dim() == 3:
+                # bsi,bso->io: batch and sequence fold into one contraction over rows
+                grad_output = grad_output.contiguous()
+                qG, SG = F.vectorwise_quant(grad_output.view(-1, grad_output.shape[2]), dim=0, quant_type=quant_type)
+                qA, SA = F.vectorwise_quant(A.contiguous().view(-1, A.shape[2]), dim=0, quant_type=quant_type)
+                grad_B = F.vectorwise_mm_dequant(F.igemm(qA.t(), qG), SA.t(), SG, grad_output.dtype, quant_type)
+            else:
+                dims = [0, 1] if A.dim() == 3 else [0]
+                qG, SG = F.vectorwise_quant(grad_output, dim=dims, quant_type=quant_type)
+                qA, SA = F.vectorwise_quant(A, dim=dims, quant_type=quant_type)
+                grad_B = F.vectorwise_mm_dequant(F.igemm(_swap_last_two(qA), qG), _swap_last_two(SA), SG,
+                                                 grad_output.dtype, quant_type)
+
+        if A.requires_grad:
+            if precision[2] != 8:
+                with torch.no_grad():
+                    grad_A = torch.matmul(grad_output, _swap_last_two(B))
+            else:
+                dims = [2] if grad_output.dim() == 3 else [1]
+                qG, SG = F.vectorwise_quant(grad_output, dim=dims, quant_type=quant_type)
+                qB, SB = F.vectorwise_quant(B, dim=dims if B.dim() == 3 else [1], quant_type=quant_type)
+                grad_A = F.vectorwise_mm_dequant(F.igemm(qG, _swap_last_two(qB)), SG, _swap_last_two(SB),
+                                                 grad_output.dtype, quant_type)
+
+        return grad_A, grad_B, None, None, None
+
+
+mm_cublas = MatMul8bit.apply
+bmm_cublas = MatMul8bit.apply
+matmul_cublas = MatMul8bit.apply
+
+
 # ----------------------------------------------------------------------------- 4-bit
 def _weight_is_transposed_view(B: torch.Tensor) -> bool:
     """Linear4bit hands matmul_4bit `weight.t()` -- shape (1, n/2) over the packed storage (n/2, 1) -- meaning

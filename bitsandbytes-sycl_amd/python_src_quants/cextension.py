@@ -39,6 +39,8 @@ class BNBNativeLibrary:
         lib.cigemmlt_workspace_bytes.restype = ct.c_longlong
         lib.chgemm_tn_workspace_bytes.restype = ct.c_longlong
         lib.cipc_allgather_buffer_bytes.restype = ct.c_longlong
+        lib.cigemm.restype = None
+        lib.cbatched_igemm.restype = None
         lib.cipc_alloc.restype = ct.c_void_p
         lib.cipc_alloc.argtypes = [ct.c_longlong, ct.POINTER(ct.c_int)]
         for name in ("cigemmlt_turing_32", "cigemmlt_turing_8", "cigemmlt_turing_8_rowscale",

@@ -1566,6 +1566,234 @@ def igemm_rowmajor(A: Tensor, B: Tensor, out: Optional[Tensor] = None) -> Tensor
     return out
 
 
+# ----------------------------------------------------------------------------- plain int8 matmul (igemm family)
+_MATMUL_K = {  # (rank A, rank B) -> per (transposed_A, transposed_B): (index of k in A.shape, index of k in B.shape)
+    (2, 2): {(False, False): (1, 0), (True, False): (0, 0), (True, True): (0, 1), (False, True): (1, 1)},
+    (3, 2): {(False, False): (2, 0), (True, False): (1, 0), (True, True): (1, 1), (False, True): (2, 1)},
+    (3, 3): {(False, False): (2, 1), (True, False): (1, 1), (True, True): (1, 2), (False, True): (2, 2)},
+}
+
+
+def check_matmul(A, B, out, transposed_A, transposed_B, expected_type=torch.int8):
+    """Shape and dtype rules of the int8 matmul (ref:functional.py:1877-1958): returns the output shape, raises
+    TypeError on a wrong dtype and ValueError when the inner dimensions disagree.  With `out` given, the
+    contraction bsi,bso->io of two 3-D tensors is accepted too, and out's shape is returned."""
+    if A.dtype != expected_type or B.dtype != expected_type:
+        raise TypeError(f"Expected torch.int8 input tensors A and B, but got {A.dtype} and {B.dtype}")
+    sA, sB = A.shape, B.shape
+    tA, tB = bool(transposed_A), bool(transposed_B)
+    rule = _MATMUL_K.get((len(sA), len(sB)))
+    correct = out is not None    # ranks outside the table have no output shape of their own
+    if rule is not None:
+        ka, kb = rule[(tA, tB)]
+        correct = sA[ka] == sB[kb]
+    sout = None
+    if out is not None:
+        sout = out.shape
+        if not correct and len(sA) == 3 and len(sB) == 3:
+            # the contraction of the backward pass: bsi,bso->io
+            if sout[0] == sA[2] and sout[1] == sB[2] and sA[0] == sB[0] and sA[1] == sB[1]:
+                correct = True
+    elif rule is not None:
+        ka, kb = rule[(tA, tB)]
+        rows = sA[len(sA) - 1 if ka == len(sA) - 2 else len(sA) - 2]
+        cols = sB[len(sB) - 1 if kb == len(sB) - 2 else len(sB) - 2]
+        sout = (sA[0], rows, cols) if len(sA) == 3 else (rows, cols)
+    if not correct:
+        raise ValueError(
+            f"Tensor dimensions incorrect for matrix mulitiplication: A x B: {sA} x {sB} with transpose for A x B: {tA} x {tB}.",
+        )
+    return sout
+
+
+_INT32_MAX = 2**31 - 1
+
+
+def _igemm_layout(t: Tensor) -> Optional[Tuple[bool, int]]:
+    """How the kernel can read the last two dims [rows, cols] of `t` in place: (False, ld) when element (i, j) is
+    at i * ld + j, (True, ld) when it is at j * ld + i, None when neither holds (the caller makes a copy)."""
+    r, c = t.shape[-2], t.shape[-1]
+    sr, sc = t.stride(-2), t.stride(-1)
+    if (sc == 1 or c == 1) and (r == 1 or sr >= c):
+        ld = sr if r > 1 else c
+        return (False, ld) if ld <= _INT32_MAX else None
+    if (sr == 1 or r == 1) and (c == 1 or sc >= r):
+        ld = sc if c > 1 else r
+        return (True, ld) if ld <= _INT32_MAX else None
+    return None
+
+
+def _igemm_operand(t: Tensor) -> Tuple[Tensor, bool, int]:
+    """(tensor, transposed, ld) of a 2-D or 3-D operand; a batch must be dense, batch stride = rows * cols."""
+    lay = _igemm_layout(t)
+    if lay is not None and t.dim() == 3 and t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.shape[2]:
+        lay = None
+    if lay is None:
+        t = t.contiguous()
+        lay = (False, max(t.shape[-1], 1))
+    return t, lay[0], lay[1]
+
+
+def _igemm_launch(X: Tensor, Y: Tensor, out: Tensor) -> Tensor:
+    """out[..., i, j] = sum_k X[..., i, k] * Y[..., k, j] on int8 views of any strides (both 2-D or both 3-D), exact
+    int32.  Row-major tensors are the transposes of the column-major matrices of cigemm / cbatched_igemm, so the
+    call computes out^T = Y^T . X^T: the library's A is Y, its B is X."""
+    batched = X.dim() == 3
+    m, k, n = X.shape[-2], X.shape[-1], Y.shape[-1]
+    nb = X.shape[0] if batched else 1
+    if out.numel() == 0:
+        return out
+    if k == 0:
+        return out.zero_()
+    dst = out
+    if out.dtype != torch.int32 or not out.is_contiguous():
+        dst = torch.empty(out.shape, dtype=torch.int32, device=out.device)
+    X, tX, ldx = _igemm_operand(X)
+    Y, tY, ldy = _igemm_operand(Y)
+    prev_device = pre_call(X.device)
+    is_on_gpu([Y, X, dst])
+    args = (None, ct.c_bool(tY), ct.c_bool(tX), ct.c_int32(n), ct.c_int32(m), ct.c_int32(k), get_ptr(Y), get_ptr(X),
+            get_ptr(dst), ct.c_int32(ldy), ct.c_int32(ldx), ct.c_int32(n))
+    if batched:
+        lib.cbatched_igemm(*args, ct.c_long(k * n), ct.c_long(m * k), ct.c_long(m * n), ct.c_int32(nb))
+    else:
+        lib.cigemm(*args)
+    post_call(prev_device)
+    if dst is not out:
+        out.copy_(dst)
+    return out
+
+
+def _check_out_shape(out: Tensor, shape) -> None:
+    """check_matmul takes a given `out` on trust; the kernel writes shape[-2] x shape[-1] per batch, so refuse others."""
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"Expected an output tensor of shape {tuple(shape)} for this product, but got {tuple(out.shape)}")
+
+
+def igemm(A: Tensor, B: Tensor, out: Optional[torch.Tensor] = None, transposed_A=False, transposed_B=False):
+    """Exact int8 x int8 -> int32 matrix product of the tensors as passed, whatever their strides
+    (ref:functional.py:2063-2161): 2-D x 2-D, 3-D x 2-D, 3-D x 3-D batched, and with `out` given the contraction
+    bsi,bso->io.  A transposed view (`X.t()`, `X.permute(0, 2, 1)`) is read in place by the K-strided kernel;
+    `transposed_A` / `transposed_B` swap the last two dims of the operand they name."""
+    sout = check_matmul(A, B, out, transposed_A, transposed_B)
+    if A.dim() == 3 and B.dim() == 3:
+        a = A.transpose(1, 2) if transposed_A else A
+        b = B.transpose(1, 2) if transposed_B else B
+        if a.shape[0] == b.shape[0] and a.shape[2] == b.shape[1] and (out is None or out.dim() == 3):
+            return batched_igemm(A, B, out, transposed_A, transposed_B)
+        # special case: bsi,bso->io
+        if not (A.shape[0] == B.shape[0] and A.shape[1] == B.shape[1]):
+            raise ValueError(
+                f"Only bsi,bso->io supported for tensor contractions, but dims for A x B were: {A.shape} x {B.shape}",
+            )
+        _check_out_shape(out, (A.shape[2], B.shape[2]))
+        return _igemm_launch(A.reshape(-1, A.shape[2]).t(), B.reshape(-1, B.shape[2]), out)
+    if out is None:
+        out = torch.empty(size=tuple(sout), dtype=torch.int32, device=A.device)
+    a = A.transpose(-1, -2) if transposed_A else A
+    b = B.transpose(-1, -2) if transposed_B else B
+    _check_out_shape(out, tuple(a.shape[:-1]) + (b.shape[-1],))
+    if a.dim() == 3:
+        # 3-D x 2-D: the batch folds into the rows (a view when A is contiguous)
+        a2 = a.reshape(-1, a.shape[2])
+        if out.is_contiguous() and out.dtype == torch.int32:
+            _igemm_launch(a2, b, out.view(a2.shape[0], b.shape[1]))
+        else:
+            out.copy_(_igemm_launch(a2, b, torch.empty((a2.shape[0], b.shape[1]), dtype=torch.int32,
+                                                       device=A.device)).view(out.shape))
+        return out
+    return _igemm_launch(a, b, out)
+
+
+def batched_igemm(A: Tensor, B: Tensor, out: Optional[torch.Tensor] = None, transposed_A=False, transposed_B=False):
+    """Batched exact int8 product [b, m, k] @ [b, k, n] -> int32 [b, m, n] (ref:functional.py:2164-2257).  Contiguous
+    tensors and their `permute(0, 2, 1)` views are read in place; any other layout is made contiguous first."""
+    if not len(A.shape) == 3 or not len(B.shape) == 3:
+        raise ValueError(f"Expected 3-dimensional tensors for bmm, but got shapes A and B: {A.shape} and {B.shape}")
+    sout = check_matmul(A, B, out, transposed_A, transposed_B)
+    if out is None:
+        out = torch.empty(size=tuple(sout), dtype=torch.int32, device=A.device)
+    a = A.transpose(1, 2) if transposed_A else A
+    b = B.transpose(1, 2) if transposed_B else B
+    _check_out_shape(out, (a.shape[0], a.shape[1], b.shape[2]))
+    return _igemm_launch(a, b, out)
+
+
+C = 127.0
+
+
+def vectorwise_quant(x, dim=1, quant_type="vector"):
+    """int8 (or, for the zeropoint kinds, integer-valued float) quantisation of `x` with one scale per tensor
+    ('linear', 'zeropoint') or per slice along `dim` (ref:functional.py:2789-2830); plain torch, any device.
+    'truncated-vector' clamps `x` in place at 0.7 of each slice's absmax first.  Unknown kinds return None."""
+    if quant_type == "linear":
+        max1 = torch.abs(x).max().float()
+        return torch.round(x / max1 * 127).to(torch.int8), max1
+    if quant_type in ("vector", "row"):
+        max1 = torch.amax(torch.abs(x), dim=dim, keepdim=True)
+        return torch.round(x * (C / max1)).to(torch.int8), max1
+    if quant_type in ("zeropoint", "vector-zeropoint", "row-zeropoint"):
+        x = x.float()
+        if quant_type == "zeropoint":
+            minx = x.min()
+            dyna = x.max() - minx
+            if dyna == 0:
+                dyna = 1
+        else:
+            minx = torch.amin(x, dim=dim, keepdim=True)
+            dyna = torch.amax(x, dim=dim, keepdim=True) - minx
+            dyna[dyna == 0] = 1
+        qx = 255.0 / dyna
+        zpx = torch.round(minx * qx)
+        return torch.round(qx * x - zpx) + zpx, qx
+    if quant_type == "truncated-vector":
+        with torch.no_grad():
+            absx = torch.abs(x)
+            max1 = torch.amax(absx, dim=dim, keepdim=True) * 0.7
+            cap = max1.expand_as(absx)
+            idx = absx > cap
+            x[idx] = cap[idx] * torch.sign(x[idx])
+            xq = torch.round(x / max1 * C).to(torch.int8)
+        return xq, max1
+    return None
+
+
+def vectorwise_dequant(xq, max1, quant_type="vector"):
+    """Inverse of vectorwise_quant for 'vector' (ref:functional.py:2833-2838); other kinds return None."""
+    if quant_type == "vector":
+        return (xq / C * max1).to(torch.float32)
+    return None
+
+
+def vectorwise_mm_dequant(xq, S1, S2, dtype=torch.half, quant_type="vector"):
+    """Scale the int32 product of two vectorwise_quant operands back by their statistics S1 (rows) and S2 (columns)
+    and cast to `dtype` (ref:functional.py:2841-2897); the arithmetic is fp32, in the reference's order."""
+    if quant_type == "linear":
+        norm = S1 * S2 / (C * C)
+        return (xq.float() * norm).to(dtype)    # scaled in fp32: the int32 sums overflow fp16
+    if quant_type == "zeropoint":
+        norm = 1.0 / (S1 * S2)
+        return (xq.float() * norm).to(dtype)
+    if quant_type not in ("row-zeropoint", "vector-zeropoint", "row", "truncated-vector", "vector"):
+        return None
+    x = xq.float()
+    if len(S1.shape) == 3 and len(x.shape) == 2:
+        S1 = S1.squeeze(0)
+    if len(S2.shape) == 3 and len(x.shape) == 2:
+        S2 = S2.squeeze(0)
+    if quant_type == "row-zeropoint":
+        x *= 1.0 / (S1 * S2)
+    elif quant_type == "vector-zeropoint":
+        x *= 1.0 / S1
+        x *= 1.0 / S2.t()
+    elif quant_type == "row":
+        x *= S1 * S2 / (C * C)
+    else:
+        x *= S1 / C
+        x *= S2 / C
+    return x.to(dtype)
+
+
 def get_colrow_absmax(A, row_stats=None, col_stats=None, nnz_block_ptr=None, threshold=0.0):
     """Row and column absmax of an fp16 matrix (ref:functional.py:2400-2435)."""
     assert A.dtype == torch.float16

@@ -202,6 +202,15 @@ int cigemmlt_turing_8_rowscale(int m, int n, int k, const int8_t* A, const int8_
 int cigemmlt_ampere_32(int m, int n, int k, const int8_t* A, const int8_t* B, void* C, float* row_scale, int lda, int ldb, int ldc);          /* :309 */
 int cigemmlt_ampere_8_rowscale(int m, int n, int k, const int8_t* A, const int8_t* B, void* C, float* row_scale, int lda, int ldb, int ldc);  /* :312 */
 int cigemmlt_ampere_8(int m, int n, int k, const int8_t* A, const int8_t* B, void* C, float* row_scale, int lda, int ldb, int ldc);           /* :315 */
+/* Plain int8 GEMM, BLAS column-major: C(m x n, ldc) = op(A)(m x k) . op(B)(k x n), int8 in, int32 out, alpha 1, beta 0
+ * (ref:sycl/pythonInterface.cpp:289-293 -> gemmex / strided_gemmex, op_gemm.cpp:263-301).  `context` is accepted and
+ * ignored.  Any m, n, k >= 1, any ld >= the contiguous extent, any byte alignment; nothing outside C's m x n elements is
+ * written.  No workspace, no allocation (safe under stream capture).  Non-positive sizes return without a launch;
+ * errors are reported through cget_last_error*.  The batch strides are in elements. */
+void cigemm(void* context, bool transposeA, bool transposeB, int m, int n, int k, void* A, void* B, void* C, int lda,
+            int ldb, int ldc);
+void cbatched_igemm(void* context, bool transposeA, bool transposeB, int m, int n, int k, void* A, void* B, void* C,
+                    int lda, int ldb, int ldc, long strideA, long strideB, long strideC, int batchCount);
 /* [additive] row-major operands: fused igemmlt + dequant_mm_int32_fp16 (fp16 [m, n] out), and exact int32 */
 int cigemmlt_row_dequant_fp16(int m, int n, int k, const int8_t* A, const int8_t* B, bnb_fp16* out, const float* rowStats,
                               const float* colStats, const bnb_fp16* bias, int lda, int ldb, int ldc);
