@@ -293,7 +293,8 @@ def _weight_is_transposed_view(B: torch.Tensor) -> bool:
 
 class MatMul4Bit(torch.autograd.Function):
     """4-bit weight matmul (ref:autograd/_functions.py:486-540): forward through functional.gemm_4bit for the
-    A @ W^T orientation, dequantise + matmul otherwise; backward grad_A = grad @ dequantize_4bit(W)."""
+    A @ W^T orientation, dequantise + matmul otherwise; backward grad_A = grad @ dequantize_4bit(W), through
+    functional.gemm_4bit_dgrad (transposing dequantise + k_hgemm) for a bf16 / fp16 gradient of that orientation."""
 
     @staticmethod
     def forward(ctx, A, B, out=None, bias=None, quant_state: Optional[F.QuantState] = None):
@@ -320,7 +321,11 @@ class MatMul4Bit(torch.autograd.Function):
         _, B = ctx.tensors
         grad_bias = grad_output.sum(0, dtype=ctx.dtype_bias) if need_bias else None
         grad_A = None
-        if need_A:
+        if need_A and _weight_is_transposed_view(B) and F.gemm_4bit_dgrad_supported(grad_output, ctx.state):
+            # out = A @ W^T with a bf16 / fp16 gradient: grad @ W by the transposing dequantise into the weight
+            # workspace + k_hgemm (functional.gemm_4bit_dgrad); the untransposed orientation needs grad @ W^T
+            grad_A = F.gemm_4bit_dgrad(grad_output, B, ctx.state)
+        elif need_A:
             grad_A = torch.matmul(grad_output, F.dequantize_4bit(B, ctx.state).to(grad_output.dtype).t())
         return grad_A, None, None, grad_bias, None
 

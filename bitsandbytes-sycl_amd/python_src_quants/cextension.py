@@ -57,6 +57,14 @@ class BNBNativeLibrary:
                      "cipc_handle_size", "cipc_get_handle", "cipc_open_handle", "cipc_close_handle", "callgather_ipc_16",
                      "cprobe_lds_poison", "cprobe_lds_peek", "croctx_enabled"):
             getattr(lib, name).restype = ct.c_int
+        # the transposing 4-bit dequantise (dequant_t.hip): (A, absmax, out, blocksize, rows, cols, ldo) and the nested
+        # form (A, absmax_q, code2, absmax2, offset, out, blocksize, blocksize2, rows, cols, ldo)
+        for t in ("bf16", "fp16"):
+            for q in ("nf4", "fp4"):
+                fn = getattr(lib, f"cdequantize_blockwise_t_{t}_{q}")
+                fn.restype, fn.argtypes = ct.c_int, [ct.c_void_p] * 3 + [ct.c_int] * 4
+                fn = getattr(lib, f"cdequantize_blockwise_nested_t_{t}_{q}")
+                fn.restype, fn.argtypes = ct.c_int, [ct.c_void_p] * 6 + [ct.c_int] * 5
 
     def __getattr__(self, item):
         fn = getattr(self._lib, item)

@@ -621,6 +621,65 @@ def dequantize_4bit(A: Tensor, quant_state: Optional[QuantState] = None, absmax:
     return out
 
 
+def _dequant_4bit_t_launch(A: Tensor, state: QuantState, out: Tensor, absmax: Optional[Tensor] = None) -> int:
+    """cdequantize_blockwise{,_nested}_t_*: the packed [N, K] weight into out[k, n] (out: [K, N] bf16/fp16 rows of
+    stride out.stride(0), unit column stride).  Compressed statistics are decoded in the kernel where it can
+    (_nested_stats_in_kernel_ok), else resolved first; `absmax` hands over already resolved fp32 statistics.  Returns
+    the C code: 0 launched, 1 not supported (nothing launched); a launch error raises."""
+    N, K = state.shape[0], state.shape[1]
+    qt = "fp4" if state.quant_type == "fp4" else "nf4"
+    Ac = A if A.is_contiguous() else A.contiguous()
+    tail = (state.blocksize, N, K, out.stride(0))
+    if absmax is None and state.nested and _nested_stats_in_kernel_ok(state):
+        s2 = state.state2
+        offset = _offset_on(state, A.device)
+        prev_device = pre_call(A.device)
+        is_on_gpu([Ac, state.absmax, s2.code, s2.absmax, offset, out])
+        fn = getattr(lib, f"cdequantize_blockwise_nested_t_{_QB[out.dtype]}_{qt}")
+        rc = fn(Ac.data_ptr(), state.absmax.data_ptr(), s2.code.data_ptr(), s2.absmax.data_ptr(), offset.data_ptr(),
+                out.data_ptr(), tail[0], s2.blocksize, *tail[1:])
+    else:
+        if absmax is None:
+            absmax = _absmax_fp32(state)
+        if absmax.dtype != torch.float32 or not absmax.is_contiguous():
+            absmax = absmax.float().contiguous()
+        prev_device = pre_call(A.device)
+        is_on_gpu([Ac, absmax, out])
+        fn = getattr(lib, f"cdequantize_blockwise_t_{_QB[out.dtype]}_{qt}")
+        rc = fn(Ac.data_ptr(), absmax.data_ptr(), out.data_ptr(), *tail)
+    post_call(prev_device)
+    if rc == 2:
+        raise RuntimeError(f"bitsandbytes HIP kernel error: {lib.cget_last_error_message().decode()}")
+    return rc
+
+
+def dequantize_4bit_t(A: Tensor, quant_state: QuantState, out: Optional[Tensor] = None) -> Tensor:
+    """The transposed dequantisation of a 4-bit [N, K] weight: a [K, N] tensor with the bits of
+    dequantize_4bit(A, quant_state).t().contiguous(), in out's dtype (quant_state.dtype without out) -- one rounding
+    from the fp32 code * absmax product.  bf16 / fp16 with N % 8 == 0 and K % 8 == 0 run the transposing kernel
+    (dequant_t.hip: no [N, K] intermediate); `out` may be a [K, N] window of a wider buffer (unit column stride, row
+    stride % 8 == 0, 16-B aligned).  Every other case (fp32, other shapes or strides) dequantises untransposed and
+    copies the transpose, so the function is total."""
+    if A.device.type != "cuda":
+        raise NotImplementedError(f"Device type not supported for 4-bit dequantization: {A.device.type}")
+    if len(quant_state.shape) != 2:
+        raise ValueError(f"dequantize_4bit_t takes a 2-D weight, got shape {tuple(quant_state.shape)}")
+    N, K = quant_state.shape[0], quant_state.shape[1]
+    if out is None:
+        out = torch.empty((K, N), dtype=quant_state.dtype, device=A.device)
+    elif tuple(out.shape) != (K, N):
+        raise ValueError(f"dequantize_4bit_t: out must be [{K}, {N}], got {tuple(out.shape)}")
+    if N == 0 or K == 0:
+        return out
+    if (out.dtype in (torch.float16, torch.bfloat16) and out.stride(1) == 1
+            and _dequant_4bit_t_launch(A, quant_state, out) == 0):
+        return out
+    W = torch.empty((N, K), dtype=out.dtype, device=A.device)
+    dequantize_4bit(A, quant_state, out=W)
+    out.copy_(W.t())
+    return out
+
+
 # ----------------------------------------------------------------------------- 4-bit matmul
 class _GemvPlan:
     """The per-weight part of a decode GEMV call, prepared once: the entry point (with ctypes argtypes, so
@@ -1368,6 +1427,110 @@ def gemm_4bit(A: Tensor, B: Tensor, state: QuantState, out: Optional[Tensor] = N
         ev[2].record()
         events.append(("gemm", ev[0], ev[2]))
     return out.view(*A.shape[:-1], N)
+
+
+# The input gradient of a 4-bit layer, grad[..., N] @ W[N, K] (MatMul4Bit.backward; QLoRA: once per frozen projection
+# per step).  k_hgemm contracts over the contiguous dimension of both operands, so the weight is dequantised already
+# transposed (dequantize_4bit_t, W^T [K, N]) into the weight workspace and the product is the chgemm_tn_* call
+# m = rows, n = K, k = N: no [N, K] allocation per backward, one rounding into the gradient's dtype, no vendor GEMM.
+# GEMM_4BIT_DGRAD_MIN_ROWS: below this many gradient rows the static route is "library" (the previous expression).
+# Measured (tools/dgrad_probe.py, profiles/lab/dgrad_probe.txt; Llama-2-7B weights, bf16, nested NF4, graph replay):
+# "hgemm" is ahead at 4096 / 256 / 16 rows on [4096, 4096] (0.88 / 0.77 / 0.92 of the library pair's time) and on
+# [11008, 4096] (0.89 / 0.69 / 0.61), and at 4096 / 256 / 128 rows on [4096, 11008] (0.74 / 0.87 / 0.95) -- so no
+# row threshold: it would give away 8-40 % on the first two weights.  The one loss is the wide product of the
+# down-projection, [4096, 11008] up to 64 rows (1.05-1.09: 46-48 against 42-46 us; k_hgemm at m <= 64, n = 11008),
+# which GEMM_4BIT_DGRAD_WIDE_MAX_ROWS leaves on the library pair: up to that many rows where K >= 2 N.
+GEMM_4BIT_DGRAD_MIN_ROWS = 1
+GEMM_4BIT_DGRAD_WIDE_MAX_ROWS = 64
+GEMM_4BIT_DGRAD_ROUTES = ("hgemm", "library")
+
+
+def gemm_4bit_dgrad_shape_ok(rows: int, N: int, K: int) -> bool:
+    """The shapes the "hgemm" route of gemm_4bit_dgrad takes: the contraction N in whole 64-wide k-tiles of k_hgemm,
+    K % 8 == 0 for the transposing dequantise, one launch's 32-bit offsets (_hgemm_fits with n = K, k = N; the
+    dequantise's 2 GiB of output).  There is no chunked form."""
+    return N % 64 == 0 and K % 8 == 0 and _hgemm_fits(rows, K, N) and K * N < 2 ** 31
+
+
+def gemm_4bit_dgrad_supported(G: Tensor, state: QuantState) -> bool:
+    """Whether gemm_4bit_dgrad runs G @ W on the project's kernels: a bf16 / fp16 gradient [..., N] against a 2-D
+    weight whose shape passes gemm_4bit_dgrad_shape_ok."""
+    if G.dtype not in (torch.bfloat16, torch.float16) or len(state.shape) != 2 or G.dim() < 1:
+        return False
+    N, K = state.shape[0], state.shape[1]
+    if G.shape[-1] != N or state.blocksize < 64:
+        return False
+    rows = G.numel() // N if N else 0
+    return gemm_4bit_dgrad_shape_ok(rows, N, K)
+
+
+def gemm_4bit_dgrad_static_route(rows: int, N: int, K: int, dtype=torch.bfloat16) -> str:
+    """The deterministic route of the input gradient: "hgemm" (dequantize_4bit_t + k_hgemm) where the shape rule holds for a 16-bit gradient of at least
+    GEMM_4BIT_DGRAD_MIN_ROWS rows -- except up to GEMM_4BIT_DGRAD_WIDE_MAX_ROWS rows against a weight with K >= 2 N,
+    where the library pair measured 4-8 % ahead -- else "library" (dequantize_4bit + torch.matmul)."""
+    if (dtype in (torch.bfloat16, torch.float16) and rows >= GEMM_4BIT_DGRAD_MIN_ROWS
+            and not (rows <= GEMM_4BIT_DGRAD_WIDE_MAX_ROWS and K >= 2 * N)
+            and gemm_4bit_dgrad_shape_ok(rows, N, K)):
+        return "hgemm"
+    return "library"
+
+
+def gemm_4bit_dgrad(G: Tensor, B: Tensor, state: QuantState, out: Optional[Tensor] = None,
+                    absmax: Optional[Tensor] = None, _route: Optional[str] = None) -> Tensor:
+    """G[..., N] @ W[N, K] -> [..., K] with W the dequantised 4-bit weight: the input gradient of out = A @ W^T.
+    Route "hgemm": the weight dequantised transposed, once rounded into G's dtype, into the weight workspace
+    (dequantize_4bit_t), then k_hgemm (chgemm_tn_ws_*, split-K over the GEMM workspace on small grids); the workspace
+    then holds W^T, so a later gemm_4bit(..., reuse_weight=True) dequantises again.  Route "library": the expression
+    MatMul4Bit.backward used before, torch.matmul(G, dequantize_4bit(B, state).to(G.dtype).t()) -- the static route
+    outside gemm_4bit_dgrad_supported, below GEMM_4BIT_DGRAD_MIN_ROWS rows and for few rows against a wide weight
+    (gemm_4bit_dgrad_static_route).  _route forces one (internal).
+    absmax: already resolved fp32 block statistics (the "hgemm" route's dequantise uses them as given)."""
+    if G.device.type != "cuda":
+        raise NotImplementedError(f"Device type not supported for the 4-bit input gradient: {G.device.type}")
+    N, K = state.shape[0], state.shape[1]
+    supported = gemm_4bit_dgrad_supported(G, state)
+    rows = G.numel() // N if N else 0
+    route = gemm_4bit_dgrad_static_route(rows, N, K, G.dtype) if supported else "library"
+    if _route is not None:
+        if _route not in GEMM_4BIT_DGRAD_ROUTES:
+            raise ValueError(f"gemm_4bit_dgrad: unknown route {_route!r}")
+        if _route == "hgemm" and not supported:
+            raise ValueError("gemm_4bit_dgrad: route 'hgemm' needs a bf16/fp16 gradient, out_features % 64 == 0, "
+                             "in_features % 8 == 0 and one launch's 32-bit offsets")
+        route = _route
+    if route == "library" or rows == 0:
+        # (dequantize_4bit hands back W^T for the transposed view Linear4bit passes, shape (1, n/2), and W otherwise:
+        # for that view this is MatMul4Bit.backward's expression as it was; the product is G @ W for either view)
+        Wd = dequantize_4bit(B, state).to(G.dtype)
+        res = torch.matmul(G, Wd.t() if B.shape[0] == 1 else Wd)
+        if out is None:
+            return res
+        out.view(res.shape).copy_(res)
+        return out.view(res.shape)
+    G2 = G.reshape(-1, N)
+    if not G2.is_contiguous() or G2.data_ptr() % 16:
+        G2 = G2.contiguous()
+    if out is None:
+        out = torch.empty((rows, K), dtype=G.dtype, device=G.device)
+    Bc = B if B.is_contiguous() else B.contiguous()
+    key = (G.device, G.dtype, _stream_key(G.device))
+    Wt = _dequant_workspace(G.device, G.dtype, K * N).view(K, N)
+    # the workspace stops holding a forward-orientation weight here: reuse_weight must not trust it
+    _DEQ_META.pop(key, None)
+    if _dequant_4bit_t_launch(Bc, state, Wt, absmax) != 0:
+        raise RuntimeError("bitsandbytes HIP transposing dequantise declined a shape gemm_4bit_dgrad_supported accepts")
+    ws_bytes = int(lib.chgemm_tn_workspace_bytes(ct.c_int32(rows), ct.c_int32(K), ct.c_int32(N)))
+    ws = _gemm_workspace(G.device, ws_bytes)
+    prev_device = pre_call(G.device)
+    is_on_gpu([G2, Wt, out])
+    fn = lib.chgemm_tn_ws_bf16 if G.dtype == torch.bfloat16 else lib.chgemm_tn_ws_fp16
+    rc = fn(ct.c_int32(rows), ct.c_int32(K), ct.c_int32(N), get_ptr(G2), ct.c_int32(N), get_ptr(Wt), ct.c_int32(N),
+            get_ptr(out), ct.c_int32(K), get_ptr(ws), ct.c_longlong(ws_bytes))
+    post_call(prev_device)
+    if rc:
+        raise RuntimeError(f"bitsandbytes HIP GEMM (chgemm_tn) returned {rc}: "
+                           f"{lib.cget_last_error_message().decode() if rc == 2 else 'shape not supported'}")
+    return out.view(*G.shape[:-1], K)
 
 
 # ----------------------------------------------------------------------------- LLM.int8

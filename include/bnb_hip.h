@@ -417,6 +417,29 @@ int cdequantize_blockwise_nested_bf16_fp4(unsigned char* A, unsigned char* absma
         float* offset, bnb_bf16* out, int blocksize, int blocksize2, long long n);
 int cdequantize_blockwise_nested_bf16_nf4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
         float* offset, bnb_bf16* out, int blocksize, int blocksize2, long long n);
+/* [additive] transposing 4-bit dequantise (dequant_t.hip): the packed weight of logical shape [rows = N, cols = K]
+ * (flat packing, element n * K + k, blocks may straddle rows) goes to out[k * ldo + n], the bits of
+ * dequantize_4bit(...).t().contiguous(): the W^T [K, N] operand of the input-gradient product grad @ W through
+ * chgemm_tn_* (m = gradient rows, n = K, k = N).  The nested form decodes compressed statistics in the kernel as
+ * cdequantize_blockwise_nested_* does.  Needs rows % 8 == 0, cols % 8 == 0, ldo >= rows, ldo % 8 == 0, a 16-B aligned
+ * out, a power-of-two blocksize >= 64 and every output byte offset below 2 GiB.  Returns 0 when launched, 1 when the
+ * shape / alignment / blocksize is not supported (nothing launched), 2 on a launch error (cget_last_error). */
+int cdequantize_blockwise_t_bf16_nf4(unsigned char* A, float* absmax, bnb_bf16* out, int blocksize, int rows, int cols,
+        int ldo);
+int cdequantize_blockwise_t_bf16_fp4(unsigned char* A, float* absmax, bnb_bf16* out, int blocksize, int rows, int cols,
+        int ldo);
+int cdequantize_blockwise_t_fp16_nf4(unsigned char* A, float* absmax, bnb_fp16* out, int blocksize, int rows, int cols,
+        int ldo);
+int cdequantize_blockwise_t_fp16_fp4(unsigned char* A, float* absmax, bnb_fp16* out, int blocksize, int rows, int cols,
+        int ldo);
+int cdequantize_blockwise_nested_t_bf16_nf4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
+        float* offset, bnb_bf16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
+int cdequantize_blockwise_nested_t_bf16_fp4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
+        float* offset, bnb_bf16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
+int cdequantize_blockwise_nested_t_fp16_nf4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
+        float* offset, bnb_fp16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
+int cdequantize_blockwise_nested_t_fp16_fp4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
+        float* offset, bnb_fp16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
 /* fp32 states: ref:sycl/pythonInterface.cpp:223-241 (reference suffixes; bf16 siblings additive).
  * max_unorm > 0 (adam, momentum, rmsprop) clips the norm of the update against max_unorm * param_norm: `unorm` then
  * points to one float, which the call overwrites with the squared L2 norm of this step's trial update (a fixed-order
