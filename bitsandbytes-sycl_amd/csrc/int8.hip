@@ -627,6 +627,14 @@ static int launch_igemm(int m, int n, int k, const int8_t* A, const int8_t* B, v
                         long long ldb, long long ldc, const float* rowStats = nullptr, const float* colStats = nullptr,
                         const fp16_t* bias = nullptr, int32_t* ws = nullptr, long long ws_bytes = 0) {
   if (m <= 0 || n <= 0 || k <= 0) return 0;
+  // 1..32 activation rows are a weight stream: igemv8.hip, the same bits in one launch without the workspace.  A forced
+  // tile kernel or split-K factor keeps the route it names.
+  if constexpr (AF == ROW && BF == ROW && EPI == EPI_F16_ROW_DEQUANT) {
+    if (g_igemm_tile == 0 && !igemm_splitk_forced()) {
+      const int rc = igemv_route(m, n, k, A, B, reinterpret_cast<fp16_t*>(C), rowStats, colStats, bias, lda, ldb, ldc);
+      if (rc != 2) return rc;
+    }
+  }
   // Row-major operands with the fused dequant on the 4-wave kernel (hgemm.hip HG_I8_DEQ, one wave per SIMD, 128 x 128
   // per wave, the three-barrier schedule) wherever its grid is one mostly full round (>= 192 tiles of 256 x 256):
   // bit-identical to igemm_256's 8 waves and faster since round 4 -- 127.3-129.3 vs 138.4-141.3 us at

@@ -51,10 +51,15 @@ bool launch_igemm_256(int m, int n, int k, const int8_t* A, const int8_t* B, voi
                       long long lda, long long ldb, long long ldc, const float* rowStats, const float* colStats,
                       const fp16_t* bias, int32_t* ws = nullptr, long long ws_bytes = 0);
 int igemm_splitk_factor(int m, int n, int k);
+bool igemm_splitk_forced();   // cigemm_set_splitk holds something other than auto
 // row-major int8 product on the 4-wave 256 x 256 kernel (hgemm.hip): 0 = launched, 1 = not covered, 2 = launch error
 int igemm_4wave(int m, int n, int k, const int8_t* A, long long lda, const int8_t* B, long long ldb, void* C,
                 long long ldc, bool dequant, const float* rowStats, const float* colStats, const fp16_t* bias);
 long long hgemm_tiles(int m, int n);
+// the 1..32-row weight-streaming kernel (igemv8.hip) under its mode and row limit (cigemv_set_mode): 0 = launched,
+// 1 = launch error, 2 = not taken (nothing launched)
+int igemv_route(int m, int n, int k, const int8_t* A, const int8_t* B, fp16_t* out, const float* rowStats,
+                const float* colStats, const fp16_t* bias, long long lda, long long ldb, long long ldc);
 long long igemm_workspace_bytes(int m, int n, int k);
 // batched int8 product with K-contiguous or K-strided operands (igemm_strided.hip):
 // Out[b][r][c] = sum_k X_b(r, k) * Y_b(c, k), X has R rows, Y has Cn rows; a K-contiguous operand has (r, k) at

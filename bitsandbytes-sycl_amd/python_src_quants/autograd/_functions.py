@@ -140,6 +140,20 @@ def _int8_product(A2, CA, SCA, state: MatmulLtState, bias, use_igemmlt: bool):
     return out
 
 
+def _decode_rows(A2, state: MatmulLtState, bias, needs_grad: bool, use_igemmlt: bool) -> bool:
+    """Whether the forward is the one-launch decode step F.int8_linear_rows: inference (no input needs a gradient)
+    without outliers on a stored row-major int8 weight, a bias the epilogue can fuse, and a row count inside the decode
+    kernel's current limit (F.int8_linear_rows_limit: the measured limit for the weight's size, or what cigemv_set_mode
+    forces)."""
+    if needs_grad or not use_igemmlt or state.threshold != 0.0 or state.has_fp16_weights or state.CB is None:
+        return False
+    if bias is not None and bias.dtype != torch.float16:
+        return False
+    rows = A2.shape[0]
+    n, k = state.CB.shape[0], A2.shape[1]
+    return rows <= F.int8_linear_rows_limit(n, k) and F.igemv_supported(rows, n, k)
+
+
 def _dequantized_weight(state: MatmulLtState, dtype) -> torch.Tensor:
     """W ~ CB * SCB / 127 in `dtype` (for grad_A = grad @ W), from CB or from the col_turing / col_ampere CxB."""
     if state.CB is not None:
@@ -166,15 +180,20 @@ class MatMul8bitLt(torch.autograd.Function):
         in_shape = A.shape
         A2 = A.reshape(-1, A.shape[-1]) if A.dim() == 3 else A
         for_backward = any(ctx.needs_input_grad[:2])
+        use_igemmlt = supports_igemmlt(A.device) and not state.force_no_igemmlt
 
-        CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, for_backward)
-        if state.has_fp16_weights:
-            B = _quantize_weight(B, state)
-        subA = _split_outliers(A2, B, CA, CAt, coo, state)
-        output = _int8_product(A2, CA, SCA, state, bias,
-                               supports_igemmlt(A.device) and not state.force_no_igemmlt)
-        if subA is not None:
-            output += torch.matmul(subA, state.subB)
+        if _decode_rows(A2, state, bias, any(ctx.needs_input_grad), use_igemmlt):
+            # 1..32 rows of inference: activation quantisation, int8 product and dequantisation in one launch
+            CAt = SCAt = subA = None
+            output = F.int8_linear_rows(A2.to(torch.float16), state.CB, state.SCB, bias=bias).to(A2.dtype)
+        else:
+            CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, for_backward)
+            if state.has_fp16_weights:
+                B = _quantize_weight(B, state)
+            subA = _split_outliers(A2, B, CA, CAt, coo, state)
+            output = _int8_product(A2, CA, SCA, state, bias, use_igemmlt)
+            if subA is not None:
+                output += torch.matmul(subA, state.subB)
 
         n_out = state.SB[0][0] if state.SB else (state.CB.shape[0] if state.CB is not None else B.shape[0])
         ctx.state = state

@@ -1684,7 +1684,10 @@ def mm_dequant(A, quant_state, row_stats, col_stats, out=None, new_row_stats=Non
 def igemmlt_dequant(CA: Tensor, CB: Tensor, row_stats: Tensor, col_stats: Tensor, bias: Optional[Tensor] = None,
                     out: Optional[Tensor] = None) -> Tensor:
     """Fused LLM.int8 matmul on row-major int8 operands: mm_dequant(igemmlt(CA, CB)) in one launch
-    (additive entry point cigemmlt_row_dequant_fp16).  CA [m, k] int8, CB [n, k] int8 -> fp16 [m, n]."""
+    (additive entry point cigemmlt_row_dequant_fp16).  CA [m, k] int8, CB [n, k] int8 -> fp16 [m, n].
+    With 1..32 rows the library routes covered shapes to the weight-streaming decode kernel (igemv8.hip) up to its
+    measured row limit -- the same bits; cigemv_set_mode forces or forbids that, and a forced cigemm_set_tile /
+    cigemm_set_splitk keeps the route it names."""
     assert CA.dtype == torch.int8 and CB.dtype == torch.int8
     m, k = CA.reshape(-1, CA.shape[-1]).shape
     n = CB.shape[0]
@@ -1708,6 +1711,96 @@ def igemmlt_dequant(CA: Tensor, CB: Tensor, row_stats: Tensor, col_stats: Tensor
         raise Exception("igemmlt ran into an error!")
     post_call(prev_device)
     return out
+
+
+IGEMV_MAX_ROWS = 32
+# Row limits of the one-launch inference forward (int8_linear_rows) in MatMul8bitLt, from tools/int8_decode_ab.py on
+# weights rotating through HBM (profiles/int8_decode_ab.json): quantising the activations inside every
+# workgroup costs VALU time that grows with the rows, so the fused step beats int8_row_quant + igemmlt_dequant up to 4
+# rows at all four measured weights and up to 8 rows for weights up to the 11008 x 4096 class; above that the layer
+# quantises once and lets igemmlt_dequant route the product.
+IGEMV_FUSED_ROWS = 4
+IGEMV_FUSED_ROWS_SMALL = 8
+IGEMV_SMALL_WEIGHT = 11008 * 4096
+
+
+def igemv_supported(rows: int, n: int, k: int) -> bool:
+    """Whether the int8 decode kernel (igemv8.hip) covers a contiguous [rows, k] x [n, k] product: 1..32 activation
+    rows, 16-B aligned operand rows (k a multiple of 16), 32-bit offsets inside a 16-row weight group."""
+    return 1 <= rows <= IGEMV_MAX_ROWS and n >= 1 and k >= 16 and k % 16 == 0 and 16 * k < 2 ** 31
+
+
+def int8_linear_rows_limit(n: int, k: int) -> int:
+    """The largest row count MatMul8bitLt's inference forward hands to int8_linear_rows for an [n, k] weight under the
+    current cigemv_set_mode: 0 when switched off, 32 when forced, the measured limits otherwise."""
+    cap = int(lib.cigemv_max_rows())
+    if cap <= 0 or cap >= IGEMV_MAX_ROWS:
+        return max(cap, 0)
+    return IGEMV_FUSED_ROWS_SMALL if n * k <= IGEMV_SMALL_WEIGHT else IGEMV_FUSED_ROWS
+
+
+def igemv_dequant(CA: Tensor, CB: Tensor, row_stats: Tensor, col_stats: Tensor, bias: Optional[Tensor] = None,
+                  out: Optional[Tensor] = None) -> Tensor:
+    """igemmlt_dequant for 1..32 activation rows on the weight-streaming decode kernel (cigemv_row_dequant_fp16): CB is
+    read once in place, one launch, no workspace; the bits are igemmlt_dequant's.  Shapes the kernel does not cover
+    (and every shape under cigemv_set_mode(-1)) take igemmlt_dequant's route."""
+    assert CA.dtype == torch.int8 and CB.dtype == torch.int8
+    m, k = CA.reshape(-1, CA.shape[-1]).shape
+    n = CB.shape[0]
+    assert CB.shape[1] == k
+    if bias is not None:
+        assert bias.dtype == torch.float16
+    if not igemv_supported(m, n, k):
+        return igemmlt_dequant(CA, CB, row_stats, col_stats, bias=bias, out=out)
+    CA2 = CA.reshape(m, k).contiguous()
+    CBc = CB.contiguous()
+    res = out if out is not None else torch.empty((m, n), dtype=torch.float16, device=CA.device)
+    prev_device = pre_call(CA.device)
+    is_on_gpu([CA2, CBc, row_stats, col_stats, res, bias])
+    rc = lib.cigemv_row_dequant_fp16(m, n, k, get_ptr(CA2), get_ptr(CBc), get_ptr(res), get_ptr(row_stats),
+                                     get_ptr(col_stats), get_ptr(bias), k, k, n)
+    post_call(prev_device)
+    if rc == 1:
+        raise Exception("igemv ran into an error!")
+    if rc != 0:
+        return igemmlt_dequant(CA2, CBc, row_stats, col_stats, bias=bias, out=out)
+    return res
+
+
+def int8_linear_rows(A: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                     row_stats: Optional[Tensor] = None) -> Tensor:
+    """The LLM.int8 inference forward without outliers for 1..32 rows in one launch (cint8_linear_rows_fp16):
+    igemmlt_dequant(*int8_row_quant(A), CB, SCB, bias) bit for bit, with the fp16 activations A [rows, k] quantised
+    inside the decode kernel; CA is never materialised.  `row_stats` (fp32 [rows]), when given, receives the row
+    statistics int8_row_quant would return.  Shapes the kernel does not cover (and every shape under
+    cigemv_set_mode(-1)) run int8_row_quant + igemmlt_dequant."""
+    assert A.dtype == torch.float16 and CB.dtype == torch.int8
+    k = A.shape[-1]
+    m = A.numel() // k if k else 0
+    n = CB.shape[0]
+    assert CB.shape[1] == k
+    if bias is not None:
+        assert bias.dtype == torch.float16
+    if row_stats is not None:
+        assert row_stats.dtype == torch.float32 and row_stats.numel() == m and row_stats.is_contiguous()
+    rc = 2
+    if igemv_supported(m, n, k):
+        A2 = A.reshape(m, k).contiguous()
+        CBc = CB.contiguous()
+        res = out if out is not None else torch.empty((m, n), dtype=torch.float16, device=A.device)
+        prev_device = pre_call(A.device)
+        is_on_gpu([A2, CBc, SCB, res, bias, row_stats])
+        rc = lib.cint8_linear_rows_fp16(m, n, k, get_ptr(A2), get_ptr(CBc), get_ptr(res), get_ptr(row_stats),
+                                        get_ptr(SCB), get_ptr(bias), k, k, n)
+        post_call(prev_device)
+        if rc == 1:
+            raise Exception("int8_linear_rows ran into an error!")
+        if rc == 0:
+            return res
+    CA, SCA = int8_row_quant(A.reshape(m, k))
+    if row_stats is not None:
+        row_stats.copy_(SCA)
+    return igemmlt_dequant(CA, CB, SCA, SCB, bias=bias, out=out)
 
 
 def igemm_rowmajor(A: Tensor, B: Tensor, out: Optional[Tensor] = None) -> Tensor:

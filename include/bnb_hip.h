@@ -225,6 +225,25 @@ int cigemmlt_row_dequant_ws_fp16(int m, int n, int k, const int8_t* A, const int
 int cigemm_row_i32_ws(int m, int n, int k, const int8_t* A, const int8_t* B, int32_t* out, int lda, int ldb,
                       int ldc, int32_t* workspace, long long workspace_bytes);
 long long cigemmlt_workspace_bytes(int m, int n, int k);
+/* [additive] LLM.int8 decode (igemv8.hip): cigemmlt_row_dequant_fp16 for 1 <= m <= 32 activation rows as a weight
+ * stream -- B [n, k] read once in place, one launch, no workspace, the same bits.  Covers k % 16 == 0, A and B and
+ * their rows 16-B aligned.  Returns 0 = launched (or m, n or k <= 0: nothing to do), 1 = error (cget_last_error),
+ * 2 = not covered or switched off (cigemv_set_mode(-1)): nothing launched, nothing written. */
+int cigemv_row_dequant_fp16(int m, int n, int k, const int8_t* A, const int8_t* B, bnb_fp16* out, const float* rowStats,
+                            const float* colStats, const bnb_fp16* bias, int lda, int ldb, int ldc);
+/* [additive] cint8_row_quant_fp16 + cigemv_row_dequant_fp16 in one launch: A is the fp16 activation matrix [m, k],
+ * quantised inside the kernel with the row kernel's expressions (the same bits); rowStats_out receives the m row
+ * statistics (NULL: not wanted); CA is never written.  Same coverage and return codes. */
+int cint8_linear_rows_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t* B, bnb_fp16* out, float* rowStats_out,
+                           const float* colStats, const bnb_fp16* bias, int lda, int ldb, int ldc);
+/* [additive, testing] which calls of cigemmlt_row_dequant{,_ws}_fp16 go to the decode kernel: 0 = auto (covered shapes
+ * up to the measured row limit, unless cigemm_set_tile / cigemm_set_splitk force a route), 1 = wherever it covers,
+ * -1 = never (the two direct entries then answer 2).  Returns the previous value. */
+int cigemv_set_mode(int mode);
+/* the largest row count that reaches the decode kernel at every covered shape under the current mode: 0 (mode -1),
+ * the automatic route's measured all-shapes limit, 8 (mode 0; weights of up to 11008 x 4096 elements are routed up to
+ * 32 rows), or the kernel's 32 (mode 1) */
+int cigemv_max_rows(void);
 /* [additive] the library GEMM of the large-prefill 4-bit path (gemm_lib.hip): C[m, n] = A[m, k] . W[n, k]^T, row-major,
  * bf16 / fp16 in and out, fp32 accumulation, on rocBLAS with a per-shape solution search (first call of a shape, per
  * quarter-octave bucket of m; kept only when > 5 % faster than the standard algorithm; none during graph capture).

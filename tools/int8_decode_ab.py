@@ -1,0 +1,156 @@
+"""A/B (GPU): the LLM.int8 decode step on the weight-streaming kernel (igemv8.hip, cigemv_set_mode(1)) against the tile
+kernels it replaces (cigemv_set_mode(-1)), same build, one process, arms alternated.
+
+For 1, 2, 4, 8, 16 and 32 activation rows and the weights [N, K] 11008 x 4096, 4096 x 11008, 4096 x 4096 and
+8192 x 28672:
+  * "product": F.igemmlt_dequant(CA, CB, SCA, SCB) alone under both modes;
+  * "forward": F.int8_row_quant + F.igemmlt_dequant under mode -1 against F.int8_linear_rows (one launch) under mode 1;
+each once with one weight replayed (hot: the Infinity Cache serves a stream that fits in it) and once rotating through
+more than 256 MB of distinct weights (HBM).  The calls of one arm are captured into a HIP graph (one call per weight
+copy) and replayed between two device events, so the host's call overhead is not in the figure; the replay count is
+calibrated to a window of at least 0.2 s, and each arm is measured REPS times, alternating with the other, so the
+spread is known.  Both routes' outputs are compared with torch.equal at every timed shape; a mismatch ends the run with
+exit status 1.
+
+Per table row: each route's median time and spread, the algorithmic bytes N*K + rows*K + 2*rows*N + 4*N, and the new
+route's share of the HBM bound (8.0 TB/s specified peak; 6.29 TB/s is what a float4 copy reaches on this part).
+Writes profiles/int8_decode_ab.json.
+
+Usage: python tools/int8_decode_ab.py [--rows 1,2,...] [--shapes 11008x4096,...] [--out FILE] [--window 0.2]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bitsandbytes-sycl_amd")]
+import python_src_quants.functional as F  # noqa: E402
+
+PEAK_SPEC_TBS = 8.0
+PEAK_COPY_TBS = 6.29
+ROTATE_BYTES = 256 * 2 ** 20
+REPS = 3
+
+
+def capture(calls):
+    for c in calls:      # warm-up: workspaces and allocator pools grow here, not inside the capture
+        c()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for c in calls:
+            c()
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def window_ms(g, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(iters):
+        g.replay()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def ab(arms, ncalls, window_s):
+    """arms: {name: graph}; returns {name: [us per call] * REPS}, arms alternated within every repetition."""
+    iters = {}
+    for name, g in arms.items():
+        ms = max(window_ms(g, 3) / 3, 1e-3)
+        iters[name] = max(3, int(window_s * 1e3 / ms) + 1)
+    res = {name: [] for name in arms}
+    for _ in range(REPS):
+        for name, g in arms.items():
+            res[name].append(window_ms(g, iters[name]) * 1e3 / iters[name] / ncalls)
+    return res
+
+
+def summarise(ts):
+    return {"median_us": statistics.median(ts), "min_us": min(ts), "max_us": max(ts)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", default="1,2,4,8,16,32")
+    ap.add_argument("--shapes", default="11008x4096,4096x11008,4096x4096,8192x28672")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "int8_decode_ab.json"))
+    ap.add_argument("--window", type=float, default=0.2)
+    args = ap.parse_args()
+    rows_list = [int(r) for r in args.rows.split(",")]
+    shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(7)
+    lib = F.lib
+    table, mismatches = [], 0
+    prev_mode = lib.cigemv_set_mode(0)
+    try:
+        for n, k in shapes:
+            copies = ROTATE_BYTES // (n * k) + 2          # > 256 MB of distinct weights
+            CBs = [torch.randint(-128, 128, (n, k), device=dev, dtype=torch.int8, generator=gen) for _ in range(copies)]
+            SCB = torch.rand(n, device=dev, generator=gen) + 0.5
+            bias = torch.randn(n, device=dev, generator=gen).half()
+            for rows in rows_list:
+                A = (torch.randn(rows, k, device=dev, generator=gen) * 3).half()
+                CA, SCA = F.int8_row_quant(A)
+                outs = {a: torch.empty(rows, n, device=dev, dtype=torch.float16) for a in ("old", "new")}
+                nbytes = n * k + rows * k + 2 * rows * n + 4 * n
+
+                def product(arm, CB):
+                    return lambda: F.igemmlt_dequant(CA, CB, SCA, SCB, bias=bias, out=outs[arm])
+
+                def forward_old(CB):
+                    def run():
+                        ca, sca = F.int8_row_quant(A)
+                        F.igemmlt_dequant(ca, CB, sca, SCB, bias=bias, out=outs["old"])
+                    return run
+
+                def forward_new(CB):
+                    return lambda: F.int8_linear_rows(A, CB, SCB, bias=bias, out=outs["new"])
+
+                for step in ("product", "forward"):
+                    for residency, ws in (("hot", [CBs[0]] * copies), ("hbm", CBs)):
+                        lib.cigemv_set_mode(-1)
+                        g_old = capture([product("old", w) if step == "product" else forward_old(w) for w in ws])
+                        lib.cigemv_set_mode(1)
+                        g_new = capture([product("new", w) if step == "product" else forward_new(w) for w in ws])
+                        # both graphs end on the last weight of the list: the outputs must be the same bytes
+                        g_old.replay()
+                        g_new.replay()
+                        torch.cuda.synchronize()
+                        equal = bool(torch.equal(outs["old"], outs["new"]))
+                        mismatches += 0 if equal else 1
+                        r = ab({"old": g_old, "new": g_new}, len(ws), args.window)
+                        old, new = summarise(r["old"]), summarise(r["new"])
+                        row = {"n": n, "k": k, "rows": rows, "step": step, "residency": residency, "copies": len(ws),
+                               "old": old, "new": new, "equal": equal, "bytes": nbytes,
+                               "new_share_of_8.0TBs": nbytes / (new["median_us"] * 1e-6) / (PEAK_SPEC_TBS * 1e12),
+                               "new_share_of_6.29TBs": nbytes / (new["median_us"] * 1e-6) / (PEAK_COPY_TBS * 1e12),
+                               # the new route wins when even its slowest repetition beats the old route's fastest
+                               "new_wins_beyond_spread": new["max_us"] < old["min_us"]}
+                        table.append(row)
+                        print(f"{n:5d} x {k:5d} rows {rows:2d} {step:8s} {residency:3s}: old {old['median_us']:8.2f} us "
+                              f"[{old['min_us']:.2f}..{old['max_us']:.2f}]  new {new['median_us']:8.2f} us "
+                              f"[{new['min_us']:.2f}..{new['max_us']:.2f}]  {row['new_share_of_8.0TBs'] * 100:5.1f} % of "
+                              f"8.0 TB/s  equal={equal}", flush=True)
+                        del g_old, g_new
+            del CBs
+            torch.cuda.empty_cache()
+    finally:
+        lib.cigemv_set_mode(prev_mode)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "reps": REPS, "window_s": args.window,
+                   "peak_spec_TBs": PEAK_SPEC_TBS, "peak_copy_TBs": PEAK_COPY_TBS, "mismatches": mismatches,
+                   "table": table}, f, indent=1)
+    print(f"wrote {args.out}; mismatches: {mismatches}")
+    return 1 if mismatches else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
