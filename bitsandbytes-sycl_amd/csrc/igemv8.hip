@@ -25,18 +25,10 @@
 // Each wave keeps two steps in flight, double buffered in registers (one buffer's loads leave before the other's
 // MFMAs wait); more would cost the second resident workgroup per CU, which is what overlaps one workgroup's start and
 // epilogue with another's stream.  The epilogue's statistics and bias are fetched at the start for the same reason.
-#include "int8_common.hpp"
+#include "igemv8_common.hpp"
 
 namespace bnb {
 
-typedef __attribute__((ext_vector_type(4))) int gv_i32x4_t;
-
-constexpr int GV_WAVES = 8;
-constexpr int GV_THREADS = 64 * GV_WAVES;
-constexpr int GV_ROWS = 16;              // weight rows per workgroup
-constexpr int GV_STEP = 256;             // k per wave step: 4 MFMAs of 64
-constexpr int GV_MAX_M = 32;             // activation rows covered
-constexpr uint32_t GV_OOB = 0x80000000u; // buffer offset beyond any resource here: the load returns zeros
 // The automatic route of cigemmlt_row_dequant{,_ws}_fp16 (mode 0), from tools/int8_decode_ab.py on weights rotating
 // through HBM (profiles/int8_decode_ab.json): up to 8 rows this kernel beats the tile kernels at all
 // four measured weights beyond the run-to-run spread; weights up to the 11008 x 4096 class (45 MB, the largest of the
@@ -45,28 +37,7 @@ constexpr int GV_AUTO_ROWS = 8;
 constexpr long long GV_SMALL_WEIGHT = 11008LL * 4096;   // N * K up to which all 32 rows are routed here
 
 static Knob<int> g_igemv_mode{0};        // cigemv_set_mode: 0 = auto, 1 = wherever covered, -1 = never
-
-__device__ __forceinline__ uint4 gv_load16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-// the weight stream: read once, non-temporal (aux 2 = nt on gfx950)
-__device__ __forceinline__ uint4 gv_load16_nt(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 2);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-// four fp16 (two dwords) -> four int8 in one dword, k_row_quant's expressions
-__device__ __forceinline__ uint32_t gv_quant4(uint32_t w0, uint32_t w1, float rsc) {
-  const uint32_t w[2] = {w0, w1};
-  uint32_t q = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = (float)__builtin_bit_cast(fp16_t, (uint16_t)(w[j >> 1] >> (16 * (j & 1))));
-    q |= (uint32_t)(uint8_t)rint_i8(__fmul_rn(a, rsc)) << (8 * j);
-  }
-  return q;
-}
+int igemv_mode() { return g_igemv_mode; }
 
 // MT: 16-row activation fragments (1: M <= 16, 2: M <= 32).  FUSED: Av is fp16 [M, K] (lda in elements), quantised
 // here; otherwise int8 [M, K] with its statistics in rowStats.
@@ -249,17 +220,6 @@ k_igemv8(int M, int N, int K, const void* __restrict__ Av, int lda, const int8_t
     out[(long long)e_token * ldc + e_col] = mm_dequant_value(
         (int32_t)sum, rs, __uint_as_float(e_cs_bits), (float)__builtin_bit_cast(fp16_t, e_bias_bits));
   }
-}
-
-// what the kernel covers, from the call's numbers alone (m, n, k > 0 here)
-static bool igemv8_covers(int m, int k, const void* A, const void* B, long long lda, long long ldb, long long ldc, int n,
-                          int a_bytes) {
-  if (m > GV_MAX_M || k % 16 != 0 || n >= (1 << 28)) return false;
-  if (lda < k || ldb < k || ldc < n) return false;
-  if ((((uintptr_t)A | (uintptr_t)B) & 15) != 0 || (lda * a_bytes) % 16 != 0 || ldb % 16 != 0) return false;
-  // 32-bit buffer offsets with the top bit free for GV_OOB
-  if ((long long)GV_ROWS * ldb >= (1LL << 31) || (long long)GV_MAX_M * lda * a_bytes >= (1LL << 31)) return false;
-  return true;
 }
 
 // 0 = launched (or nothing to do), 1 = launch error, 2 = not covered (nothing launched)

@@ -48,6 +48,9 @@ class MatmulLtState:
     has_fp16_weights = True
     memory_efficient_backward = False
     use_pool = False
+    # threshold > 0 inference of 1..32 rows in one launch (F.int8_linear_rows with the threshold).  Off by default:
+    # that kernel rounds to fp16 once, so its result is not the bits of the unfused outlier path
+    fused_outlier_decode = False
     formatB = F.get_special_format_str()
 
     def reset_grads(self):
@@ -142,16 +145,22 @@ def _int8_product(A2, CA, SCA, state: MatmulLtState, bias, use_igemmlt: bool):
 
 def _decode_rows(A2, state: MatmulLtState, bias, needs_grad: bool, use_igemmlt: bool) -> bool:
     """Whether the forward is the one-launch decode step F.int8_linear_rows: inference (no input needs a gradient)
-    without outliers on a stored row-major int8 weight, a bias the epilogue can fuse, and a row count inside the decode
-    kernel's current limit (F.int8_linear_rows_limit: the measured limit for the weight's size, or what cigemv_set_mode
-    forces)."""
-    if needs_grad or not use_igemmlt or state.threshold != 0.0 or state.has_fp16_weights or state.CB is None:
+    on a stored row-major int8 weight, a bias the epilogue can fuse, and a row count inside the decode kernel's current
+    limit (F.int8_linear_rows_limit: the measured limit for the weight's size, or what cigemv_set_mode forces).
+    Without a threshold always; with one only when the state asks for it (fused_outlier_decode) and the outlier
+    kernel covers k."""
+    if needs_grad or not use_igemmlt or state.has_fp16_weights or state.CB is None:
+        return False
+    threshold = state.threshold
+    if threshold != 0.0 and not (threshold > 0.0 and getattr(state, "fused_outlier_decode", False)):
         return False
     if bias is not None and bias.dtype != torch.float16:
         return False
     rows = A2.shape[0]
     n, k = state.CB.shape[0], A2.shape[1]
-    return rows <= F.int8_linear_rows_limit(n, k) and F.igemv_supported(rows, n, k)
+    if threshold > 0.0 and k > F.IGEMV_OUTLIER_MAX_K:
+        return False
+    return rows <= F.int8_linear_rows_limit(n, k, threshold) and F.igemv_supported(rows, n, k)
 
 
 def _dequantized_weight(state: MatmulLtState, dtype) -> torch.Tensor:
@@ -183,9 +192,11 @@ class MatMul8bitLt(torch.autograd.Function):
         use_igemmlt = supports_igemmlt(A.device) and not state.force_no_igemmlt
 
         if _decode_rows(A2, state, bias, any(ctx.needs_input_grad), use_igemmlt):
-            # 1..32 rows of inference: activation quantisation, int8 product and dequantisation in one launch
+            # 1..32 rows of inference: activation quantisation, int8 product and dequantisation in one launch; with a
+            # threshold also the outlier columns' product (state.idx / state.subB are not produced: backward's only)
             CAt = SCAt = subA = None
-            output = F.int8_linear_rows(A2.to(torch.float16), state.CB, state.SCB, bias=bias).to(A2.dtype)
+            output = F.int8_linear_rows(A2.to(torch.float16), state.CB, state.SCB, bias=bias,
+                                        threshold=state.threshold).to(A2.dtype)
         else:
             CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, for_backward)
             if state.has_fp16_weights:

@@ -56,11 +56,15 @@ class BNBNativeLibrary:
                      "cgemm_4bit_inference_nested_ws_fp16", "cset_cpu_threads", "cgemm_4bit_fewtok_takes", "chgemm_tn_ws_bf16", "chgemm_tn_ws_fp16",
                      "cipc_handle_size", "cipc_get_handle", "cipc_open_handle", "cipc_close_handle", "callgather_ipc_16",
                      "cprobe_lds_poison", "cprobe_lds_peek", "croctx_enabled",
-                     "cigemv_row_dequant_fp16", "cint8_linear_rows_fp16", "cigemv_set_mode", "cigemv_max_rows"):
+                     "cigemv_row_dequant_fp16", "cint8_linear_rows_fp16", "cigemv_set_mode", "cigemv_max_rows",
+                     "cint8_linear_rows_outlier_fp16"):
             getattr(lib, name).restype = ct.c_int
         # the int8 decode kernel (igemv8.hip): (m, n, k, A, B, out, rowStats, colStats, bias, lda, ldb, ldc)
         for name in ("cigemv_row_dequant_fp16", "cint8_linear_rows_fp16"):
             getattr(lib, name).argtypes = [ct.c_int] * 3 + [ct.c_void_p] * 6 + [ct.c_int] * 3
+        # (m, n, k, A, B, out, rowStats_out, outlier_cols_out, colStats, bias, threshold, lda, ldb, ldc)
+        lib.cint8_linear_rows_outlier_fp16.argtypes = ([ct.c_int] * 3 + [ct.c_void_p] * 7 + [ct.c_float]
+                                                       + [ct.c_int] * 3)
         lib.cigemv_set_mode.argtypes = [ct.c_int]
         lib.cigemv_max_rows.argtypes = []
         # the transposing 4-bit dequantise (dequant_t.hip): (A, absmax, out, blocksize, rows, cols, ldo) and the nested

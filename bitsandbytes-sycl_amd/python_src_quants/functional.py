@@ -1722,6 +1722,14 @@ IGEMV_MAX_ROWS = 32
 IGEMV_FUSED_ROWS = 4
 IGEMV_FUSED_ROWS_SMALL = 8
 IGEMV_SMALL_WEIGHT = 11008 * 4096
+# The same limits for the threshold > 0 forward on the outlier kernel (igemv8_outlier.hip, Linear8bitLt's
+# fused_outlier_decode), from tools/int8_decode_ab.py --threshold 6 on the same weights (whole layer forward, flag off
+# against flag on, profiles/int8_outlier_decode_ab.json): the unfused forward is ~330-420 us of launches
+# and host synchronisations whatever the shape, and the one launch beats it beyond the spread at every measured row
+# count and weight (the closest: 8192 x 28672 at 32 rows, 313 against 419 us).
+IGEMV_OUTLIER_ROWS = 32
+IGEMV_OUTLIER_ROWS_SMALL = 32
+IGEMV_OUTLIER_MAX_K = 65536         # the outlier kernel keeps one bit per column in LDS
 
 
 def igemv_supported(rows: int, n: int, k: int) -> bool:
@@ -1730,13 +1738,17 @@ def igemv_supported(rows: int, n: int, k: int) -> bool:
     return 1 <= rows <= IGEMV_MAX_ROWS and n >= 1 and k >= 16 and k % 16 == 0 and 16 * k < 2 ** 31
 
 
-def int8_linear_rows_limit(n: int, k: int) -> int:
+def int8_linear_rows_limit(n: int, k: int, threshold: float = 0.0) -> int:
     """The largest row count MatMul8bitLt's inference forward hands to int8_linear_rows for an [n, k] weight under the
-    current cigemv_set_mode: 0 when switched off, 32 when forced, the measured limits otherwise."""
+    current cigemv_set_mode: 0 when switched off, 32 when forced, the measured limits otherwise (with threshold > 0
+    those of the outlier kernel, for layers that set fused_outlier_decode)."""
     cap = int(lib.cigemv_max_rows())
     if cap <= 0 or cap >= IGEMV_MAX_ROWS:
         return max(cap, 0)
-    return IGEMV_FUSED_ROWS_SMALL if n * k <= IGEMV_SMALL_WEIGHT else IGEMV_FUSED_ROWS
+    small = n * k <= IGEMV_SMALL_WEIGHT
+    if threshold > 0.0:
+        return IGEMV_OUTLIER_ROWS_SMALL if small else IGEMV_OUTLIER_ROWS
+    return IGEMV_FUSED_ROWS_SMALL if small else IGEMV_FUSED_ROWS
 
 
 def igemv_dequant(CA: Tensor, CB: Tensor, row_stats: Tensor, col_stats: Tensor, bias: Optional[Tensor] = None,
@@ -1767,14 +1779,44 @@ def igemv_dequant(CA: Tensor, CB: Tensor, row_stats: Tensor, col_stats: Tensor, 
     return res
 
 
+def _int8_linear_rows_unfused(A2: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor], threshold: float,
+                              out: Optional[Tensor], row_stats: Optional[Tensor]) -> Tensor:
+    """The threshold > 0 inference forward as MatMul8bitLt composes it from separate launches: double_quant with the
+    threshold (host synchronisations included), every column that holds an outlier zeroed in CA, igemmlt_dequant, and
+    the fp16 product of those columns with the fp16-rounded dequantised weight columns added in fp16.  Three roundings
+    to fp16 (int8 part, outlier part, sum) plus the weight's."""
+    CA, _, SCA, _, coo = double_quant(A2, threshold=threshold)
+    if row_stats is not None:
+        row_stats.copy_(SCA)
+    if coo is None:
+        return igemmlt_dequant(CA, CB, SCA, SCB, bias=bias, out=out)
+    idx = torch.unique(coo.colidx).long()
+    CA[:, idx] = 0
+    subB = (CB[:, idx].clone() * SCB.view(-1, 1) / 127.0).t().contiguous().to(torch.float16)
+    res = igemmlt_dequant(CA, CB, SCA, SCB, bias=bias, out=out)
+    res += torch.matmul(A2[:, idx], subB)
+    return res
+
+
 def int8_linear_rows(A: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor] = None, out: Optional[Tensor] = None,
-                     row_stats: Optional[Tensor] = None) -> Tensor:
-    """The LLM.int8 inference forward without outliers for 1..32 rows in one launch (cint8_linear_rows_fp16):
-    igemmlt_dequant(*int8_row_quant(A), CB, SCB, bias) bit for bit, with the fp16 activations A [rows, k] quantised
+                     row_stats: Optional[Tensor] = None, threshold: float = 0.0) -> Tensor:
+    """The LLM.int8 inference forward for 1..32 rows in one launch, with the fp16 activations A [rows, k] quantised
     inside the decode kernel; CA is never materialised.  `row_stats` (fp32 [rows]), when given, receives the row
-    statistics int8_row_quant would return.  Shapes the kernel does not cover (and every shape under
-    cigemv_set_mode(-1)) run int8_row_quant + igemmlt_dequant."""
+    statistics.
+
+    threshold == 0 (cint8_linear_rows_fp16): igemmlt_dequant(*int8_row_quant(A), CB, SCB, bias) bit for bit; shapes
+    the kernel does not cover (and every shape under cigemv_set_mode(-1)) run int8_row_quant + igemmlt_dequant.
+
+    threshold > 0 (cint8_linear_rows_outlier_fp16): every column of A holding a value with |a| >= threshold leaves the
+    int8 product as a whole (the row statistics are get_colrow_absmax's with that threshold) and the kernel adds
+    (SCB / 127) * sum over those columns of A[r, c] * CB[j, c] in fp32 before the single rounding to fp16; no COO, no
+    host synchronisation.  Without an outlier the bits are the threshold == 0 result's.  Shapes the kernel does not
+    cover (k > 65536 among them) and mode -1 run the unfused composition of the layer (double_quant(threshold),
+    whole-column zeroing, igemmlt_dequant, fp16 outlier product), which rounds to fp16 three times and the weight
+    columns once more: it agrees with the kernel within those roundings, not bit for bit."""
     assert A.dtype == torch.float16 and CB.dtype == torch.int8
+    if not threshold >= 0.0:
+        raise ValueError(f"int8_linear_rows: threshold must be >= 0, got {threshold}")
     k = A.shape[-1]
     m = A.numel() // k if k else 0
     n = CB.shape[0]
@@ -1783,20 +1825,28 @@ def int8_linear_rows(A: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor] 
         assert bias.dtype == torch.float16
     if row_stats is not None:
         assert row_stats.dtype == torch.float32 and row_stats.numel() == m and row_stats.is_contiguous()
+    outlier = threshold > 0.0
     rc = 2
-    if igemv_supported(m, n, k):
+    if igemv_supported(m, n, k) and not (outlier and k > IGEMV_OUTLIER_MAX_K):
         A2 = A.reshape(m, k).contiguous()
         CBc = CB.contiguous()
         res = out if out is not None else torch.empty((m, n), dtype=torch.float16, device=A.device)
         prev_device = pre_call(A.device)
         is_on_gpu([A2, CBc, SCB, res, bias, row_stats])
-        rc = lib.cint8_linear_rows_fp16(m, n, k, get_ptr(A2), get_ptr(CBc), get_ptr(res), get_ptr(row_stats),
-                                        get_ptr(SCB), get_ptr(bias), k, k, n)
+        if outlier:
+            rc = lib.cint8_linear_rows_outlier_fp16(m, n, k, get_ptr(A2), get_ptr(CBc), get_ptr(res),
+                                                    get_ptr(row_stats), None, get_ptr(SCB), get_ptr(bias),
+                                                    ct.c_float(threshold), k, k, n)
+        else:
+            rc = lib.cint8_linear_rows_fp16(m, n, k, get_ptr(A2), get_ptr(CBc), get_ptr(res), get_ptr(row_stats),
+                                            get_ptr(SCB), get_ptr(bias), k, k, n)
         post_call(prev_device)
         if rc == 1:
             raise Exception("int8_linear_rows ran into an error!")
         if rc == 0:
             return res
+    if outlier:
+        return _int8_linear_rows_unfused(A.reshape(m, k).contiguous(), CB, SCB, bias, threshold, out, row_stats)
     CA, SCA = int8_row_quant(A.reshape(m, k))
     if row_stats is not None:
         row_stats.copy_(SCA)

@@ -255,10 +255,15 @@ def maybe_rearrange_weight(state_dict, prefix, local_metadata, strict, missing_k
 
 class Linear8bitLt(nn.Linear):
     """LLM.int8() linear layer (ref:nn/modules.py:657-821): int8 weight rows (CB, SCB), the activation
-    quantised per row at every forward, outlier columns above `threshold` kept in fp16."""
+    quantised per row at every forward, outlier columns above `threshold` kept in fp16.
+
+    `fused_outlier_decode` (this backend's, off by default): an inference forward of 1..32 rows with threshold > 0
+    runs as one launch (F.int8_linear_rows with the threshold), which rounds to fp16 once where the unfused path
+    rounds three times -- within a derived tolerance of it, not its bits."""
 
     def __init__(self, input_features: int, output_features: int, bias=True, has_fp16_weights=True,
-                 memory_efficient_backward=False, threshold=0.0, index=None, device=None):
+                 memory_efficient_backward=False, threshold=0.0, index=None, device=None,
+                 fused_outlier_decode=False):
         super().__init__(input_features, output_features, bias, device)
         assert not memory_efficient_backward, ("memory_efficient_backward is no longer required and the argument is "
                                                "deprecated in 0.37.0 and will be removed in 0.39.0")
@@ -267,6 +272,7 @@ class Linear8bitLt(nn.Linear):
         self.state.threshold = threshold
         self.state.has_fp16_weights = has_fp16_weights
         self.state.memory_efficient_backward = memory_efficient_backward
+        self.state.fused_outlier_decode = bool(fused_outlier_decode)
         if threshold > 0.0 and not has_fp16_weights:
             self.state.use_pool = True
         self.weight = Int8Params(self.weight.data, has_fp16_weights=has_fp16_weights, requires_grad=has_fp16_weights)

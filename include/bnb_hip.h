@@ -236,6 +236,17 @@ int cigemv_row_dequant_fp16(int m, int n, int k, const int8_t* A, const int8_t* 
  * statistics (NULL: not wanted); CA is never written.  Same coverage and return codes. */
 int cint8_linear_rows_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t* B, bnb_fp16* out, float* rowStats_out,
                            const float* colStats, const bnb_fp16* bias, int lda, int ldb, int ldc);
+/* [additive] cint8_linear_rows_fp16 with an outlier threshold (igemv8_outlier.hip), the LLM.int8 inference forward
+ * with threshold > 0 in one launch: every column of A that holds a value with |a| >= threshold leaves the int8
+ * product as a whole (its row statistics are cget_col_row_stats' with that threshold), and the fp16 x int8 product of
+ * those columns is added in fp32 before the single rounding to fp16:
+ *   out = fp16(mm_dequant's fp32 product + bias + (colStats / 127) * sum_{outlier c} A[r, c] * B[j, c]).
+ * Without an outlier the result is cint8_linear_rows_fp16's bit for bit.  rowStats_out (m floats) and
+ * outlier_cols_out (one int: the number of outlier columns) may be NULL.  Covers what cint8_linear_rows_fp16 covers
+ * with k <= 65536 and a finite threshold > 0; same return codes. */
+int cint8_linear_rows_outlier_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t* B, bnb_fp16* out,
+                                   float* rowStats_out, int* outlier_cols_out, const float* colStats,
+                                   const bnb_fp16* bias, float threshold, int lda, int ldb, int ldc);
 /* [additive, testing] which calls of cigemmlt_row_dequant{,_ws}_fp16 go to the decode kernel: 0 = auto (covered shapes
  * up to the measured row limit, unless cigemm_set_tile / cigemm_set_splitk force a route), 1 = wherever it covers,
  * -1 = never (the two direct entries then answer 2).  Returns the previous value. */

@@ -16,7 +16,17 @@ Per table row: each route's median time and spread, the algorithmic bytes N*K + 
 route's share of the HBM bound (8.0 TB/s specified peak; 6.29 TB/s is what a float4 copy reaches on this part).
 Writes profiles/int8_decode_ab.json.
 
-Usage: python tools/int8_decode_ab.py [--rows 1,2,...] [--shapes 11008x4096,...] [--out FILE] [--window 0.2]"""
+With --threshold T (> 0) the A/B is the outlier forward instead: the whole Linear8bitLt forward (threshold T, stored
+int8 weight, fp16 bias) with fused_outlier_decode off (double_quant with its host synchronisations, whole-column zeroing,
+igemmlt_dequant, fp16 outlier matmul) against the same layer with the flag on (one launch, igemv8_outlier.hip,
+cigemv_set_mode(1)), on the same shapes and rows, weights rotating through HBM.  The activations are randn (sigma 1)
+with --outlier-cols C columns (default 8) given one value of magnitude 8..60 each.  The unfused forward synchronises
+with the host, so both arms run eagerly between two device events (host time included, as a caller sees it); the
+fused arm is also replayed as a HIP graph ("fused_graph": its device time alone).  The two arms round differently (the
+fused one once): their largest difference is reported, not compared.  Writes profiles/int8_outlier_decode_ab.json.
+
+Usage: python tools/int8_decode_ab.py [--rows 1,2,...] [--shapes 11008x4096,...] [--out FILE] [--window 0.2]
+                                      [--threshold T [--outlier-cols C]]"""
 import argparse
 import json
 import os
@@ -75,15 +85,116 @@ def summarise(ts):
     return {"median_us": statistics.median(ts), "min_us": min(ts), "max_us": max(ts)}
 
 
+def eager_window_ms(calls, iters):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    for _ in range(iters):
+        for c in calls:
+            c()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def make_layer(CB, SCB, bias, threshold, fused):
+    """A Linear8bitLt around an already quantised weight (CB, SCB are shared, not copied)."""
+    from python_src_quants.nn import Int8Params, Linear8bitLt
+    n, k = CB.shape
+    lin = Linear8bitLt(16, 16, bias=True, has_fp16_weights=False, threshold=threshold, fused_outlier_decode=fused)
+    lin.in_features, lin.out_features = k, n
+    lin.weight = Int8Params(CB, requires_grad=False, has_fp16_weights=False, CB=CB, SCB=SCB)
+    lin.bias = torch.nn.Parameter(bias, requires_grad=False)
+    return lin.eval()
+
+
+def main_outlier(args, rows_list, shapes):
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(7)
+    lib = F.lib
+    table = []
+    prev_mode = lib.cigemv_set_mode(1)
+    try:
+        for n, k in shapes:
+            copies = ROTATE_BYTES // (n * k) + 2          # > 256 MB of distinct weights
+            CBs = [torch.randint(-128, 128, (n, k), device=dev, dtype=torch.int8, generator=gen) for _ in range(copies)]
+            SCB = torch.rand(n, device=dev, generator=gen) + 0.5
+            bias = torch.randn(n, device=dev, generator=gen).half()
+            layers = {arm: [make_layer(CB, SCB, bias, args.threshold, arm == "fused") for CB in CBs]
+                      for arm in ("unfused", "fused")}
+            for rows in rows_list:
+                A = torch.randn(rows, k, device=dev, generator=gen).clamp_(-5, 5).half()
+                cols = torch.randperm(k, device=dev, generator=gen)[:args.outlier_cols]
+                for i, c in enumerate(cols.tolist()):
+                    A[i % rows, c] = (8.0 + (i * 13) % 53) * (1 if i % 2 == 0 else -1)
+                outs = {}
+
+                def arm_calls(arm):
+                    def call(lin):
+                        def run():
+                            outs[arm] = lin(A)
+                        return run
+                    return [call(lin) for lin in layers[arm]]
+
+                calls = {arm: arm_calls(arm) for arm in ("unfused", "fused")}
+                with torch.no_grad():
+                    for arm in calls:                     # warm-up; both end on the last weight
+                        for c in calls[arm]:
+                            c()
+                    torch.cuda.synchronize()
+                    diff = float((outs["unfused"].float() - outs["fused"].float()).abs().max())
+                    scale = float(outs["unfused"].float().abs().max())
+                    g = capture(calls["fused"])
+                    iters = {}
+                    for arm in calls:
+                        ms = max(eager_window_ms(calls[arm], 1), 1e-3)
+                        iters[arm] = max(2, int(args.window * 1e3 / ms) + 1)
+                    g_iters = max(3, int(args.window * 1e3 / max(window_ms(g, 3) / 3, 1e-3)) + 1)
+                    res = {"unfused": [], "fused": [], "fused_graph": []}
+                    for _ in range(REPS):
+                        for arm in calls:
+                            res[arm].append(eager_window_ms(calls[arm], iters[arm]) * 1e3 / iters[arm] / copies)
+                        res["fused_graph"].append(window_ms(g, g_iters) * 1e3 / g_iters / copies)
+                    del g
+                row = {"n": n, "k": k, "rows": rows, "copies": copies, "threshold": args.threshold,
+                       "outlier_cols": args.outlier_cols, "max_abs_diff": diff, "max_abs_out": scale,
+                       **{arm: summarise(ts) for arm, ts in res.items()}}
+                # the fused forward wins when even its slowest repetition beats the unfused forward's fastest
+                row["fused_wins_beyond_spread"] = row["fused"]["max_us"] < row["unfused"]["min_us"]
+                table.append(row)
+                print(f"{n:5d} x {k:5d} rows {rows:2d} thr {args.threshold:g} cols {args.outlier_cols}: unfused "
+                      f"{row['unfused']['median_us']:8.2f} us [{row['unfused']['min_us']:.2f}.."
+                      f"{row['unfused']['max_us']:.2f}]  fused {row['fused']['median_us']:8.2f} us "
+                      f"[{row['fused']['min_us']:.2f}..{row['fused']['max_us']:.2f}]  fused graph "
+                      f"{row['fused_graph']['median_us']:8.2f} us  max |diff| {diff:.4g} of {scale:.4g}", flush=True)
+            del CBs, layers
+            torch.cuda.empty_cache()
+    finally:
+        lib.cigemv_set_mode(prev_mode)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "reps": REPS, "window_s": args.window,
+                   "threshold": args.threshold, "outlier_cols": args.outlier_cols, "table": table}, f, indent=1)
+    print(f"wrote {args.out}")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", default="1,2,4,8,16,32")
     ap.add_argument("--shapes", default="11008x4096,4096x11008,4096x4096,8192x28672")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "int8_decode_ab.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--window", type=float, default=0.2)
+    ap.add_argument("--threshold", type=float, default=0.0)
+    ap.add_argument("--outlier-cols", type=int, default=8)
     args = ap.parse_args()
     rows_list = [int(r) for r in args.rows.split(",")]
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
+    if args.out is None:
+        name = "int8_outlier_decode_ab.json" if args.threshold > 0.0 else "int8_decode_ab.json"
+        args.out = os.path.join(ROOT, "profiles", name)
+    if args.threshold > 0.0:
+        return main_outlier(args, rows_list, shapes)
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(7)
     lib = F.lib
