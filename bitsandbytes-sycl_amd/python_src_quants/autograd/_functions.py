@@ -51,6 +51,10 @@ class MatmulLtState:
     # threshold > 0 inference of 1..32 rows in one launch (F.int8_linear_rows with the threshold).  Off by default:
     # that kernel rounds to fp16 once, so its result is not the bits of the unfused outlier path
     fused_outlier_decode = False
+    # threshold > 0 inference of any row count without a host synchronisation (F.int8_linear_outliers: the outlier
+    # columns are found on the device around the int8 GEMM).  Off by default for the same reason: two roundings to
+    # fp16 where the unfused path has three, so not its bits.  fused_outlier_decode keeps its 1..32 rows when set
+    fused_outlier_prefill = False
     formatB = F.get_special_format_str()
 
     def reset_grads(self):
@@ -163,6 +167,20 @@ def _decode_rows(A2, state: MatmulLtState, bias, needs_grad: bool, use_igemmlt: 
     return rows <= F.int8_linear_rows_limit(n, k, threshold) and F.igemv_supported(rows, n, k)
 
 
+def _prefill_outliers(A2, state: MatmulLtState, bias, needs_grad: bool, use_igemmlt: bool) -> bool:
+    """Whether the forward is F.int8_linear_outliers (asked only after _decode_rows declined): the state asks for it
+    (fused_outlier_prefill), a threshold > 0, inference (no input needs a gradient) on a stored row-major int8 weight,
+    a bias the GEMM's epilogue can fuse, and a shape the device-side outlier kernels cover.  No row cap: the A/B of
+    DESIGN.md section 4c found none."""
+    if not getattr(state, "fused_outlier_prefill", False) or not state.threshold > 0.0:
+        return False
+    if needs_grad or not use_igemmlt or state.has_fp16_weights or state.CB is None:
+        return False
+    if bias is not None and bias.dtype != torch.float16:
+        return False
+    return F.int8_linear_outliers_supported(A2.shape[0], state.CB.shape[0], A2.shape[1])
+
+
 def _dequantized_weight(state: MatmulLtState, dtype) -> torch.Tensor:
     """W ~ CB * SCB / 127 in `dtype` (for grad_A = grad @ W), from CB or from the col_turing / col_ampere CxB."""
     if state.CB is not None:
@@ -197,6 +215,12 @@ class MatMul8bitLt(torch.autograd.Function):
             CAt = SCAt = subA = None
             output = F.int8_linear_rows(A2.to(torch.float16), state.CB, state.SCB, bias=bias,
                                         threshold=state.threshold).to(A2.dtype)
+        elif _prefill_outliers(A2, state, bias, any(ctx.needs_input_grad), use_igemmlt):
+            # any row count of thresholded inference: the outlier columns found on the device around the int8 GEMM, no
+            # host synchronisation (state.idx / state.subB are not produced: backward's only)
+            CAt = SCAt = subA = None
+            output = F.int8_linear_outliers(A2.to(torch.float16), state.CB, state.SCB, bias=bias,
+                                            threshold=state.threshold).to(A2.dtype)
         else:
             CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, for_backward)
             if state.has_fp16_weights:

@@ -57,7 +57,7 @@ class BNBNativeLibrary:
                      "cipc_handle_size", "cipc_get_handle", "cipc_open_handle", "cipc_close_handle", "callgather_ipc_16",
                      "cprobe_lds_poison", "cprobe_lds_peek", "croctx_enabled",
                      "cigemv_row_dequant_fp16", "cint8_linear_rows_fp16", "cigemv_set_mode", "cigemv_max_rows",
-                     "cint8_linear_rows_outlier_fp16"):
+                     "cint8_linear_rows_outlier_fp16", "cint8_outlier_quant_fp16", "cint8_outlier_side_fp16"):
             getattr(lib, name).restype = ct.c_int
         # the int8 decode kernel (igemv8.hip): (m, n, k, A, B, out, rowStats, colStats, bias, lda, ldb, ldc)
         for name in ("cigemv_row_dequant_fp16", "cint8_linear_rows_fp16"):
@@ -65,6 +65,13 @@ class BNBNativeLibrary:
         # (m, n, k, A, B, out, rowStats_out, outlier_cols_out, colStats, bias, threshold, lda, ldb, ldc)
         lib.cint8_linear_rows_outlier_fp16.argtypes = ([ct.c_int] * 3 + [ct.c_void_p] * 7 + [ct.c_float]
                                                        + [ct.c_int] * 3)
+        # the thresholded prefill (int8_outlier_prefill.hip): (k); (m, k, A, threshold, CA, rowStats, ws, ws_bytes);
+        # (m, n, k, A, B, colStats, out, ldc, ws)
+        lib.cint8_outlier_workspace_bytes.restype = ct.c_longlong
+        lib.cint8_outlier_workspace_bytes.argtypes = [ct.c_int]
+        lib.cint8_outlier_quant_fp16.argtypes = ([ct.c_int] * 2 + [ct.c_void_p, ct.c_float] + [ct.c_void_p] * 3
+                                                 + [ct.c_longlong])
+        lib.cint8_outlier_side_fp16.argtypes = [ct.c_int] * 3 + [ct.c_void_p] * 4 + [ct.c_int, ct.c_void_p]
         lib.cigemv_set_mode.argtypes = [ct.c_int]
         lib.cigemv_max_rows.argtypes = []
         # the transposing 4-bit dequantise (dequant_t.hip): (A, absmax, out, blocksize, rows, cols, ldo) and the nested

@@ -1730,6 +1730,10 @@ IGEMV_SMALL_WEIGHT = 11008 * 4096
 IGEMV_OUTLIER_ROWS = 32
 IGEMV_OUTLIER_ROWS_SMALL = 32
 IGEMV_OUTLIER_MAX_K = 65536         # the outlier kernel keeps one bit per column in LDS
+# The thresholded prefill without a host round trip (int8_linear_outliers, Linear8bitLt's fused_outlier_prefill) has no
+# row cap: tools/int8_decode_ab.py --threshold 6 --rows 64,256,1024,4096 on the same four weights, eight outlier
+# columns, and 64 columns at 4096 rows on 11008 x 4096 (profiles/int8_outlier_prefill_ab.json): its
+# slowest repetition beats the unfused forward's fastest in all 17 cells (the closest: 64 columns, 424 against 506 us).
 
 
 def igemv_supported(rows: int, n: int, k: int) -> bool:
@@ -1851,6 +1855,82 @@ def int8_linear_rows(A: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor] 
     if row_stats is not None:
         row_stats.copy_(SCA)
     return igemmlt_dequant(CA, CB, SCA, SCB, bias=bias, out=out)
+
+
+_OUTLIER_WS: dict = {}
+
+
+def _outlier_workspace(device, nbytes: int) -> Tensor:
+    """Grow-only workspace per (device, stream) of the thresholded prefill (cint8_outlier_workspace_bytes: the column
+    bit mask, the outlier count and the column list).  Its own buffer: igemmlt_dequant's split-K workspace is in use
+    between the two calls that share this one."""
+    key = (device, _stream_key(device))
+    ws = _OUTLIER_WS.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=device)
+        _OUTLIER_WS[key] = ws
+    return ws
+
+
+def int8_linear_outliers_supported(rows: int, n: int, k: int) -> bool:
+    """Whether int8_linear_outliers runs a contiguous [rows, k] x [n, k] product on the device-side outlier kernels
+    (int8_outlier_prefill.hip): any row count, 16-B activation vectors (k a multiple of 8)."""
+    return rows >= 1 and n >= 1 and k >= 8 and k % 8 == 0
+
+
+def int8_linear_outliers(A: Tensor, CB: Tensor, SCB: Tensor, bias: Optional[Tensor] = None, threshold: float = 6.0,
+                         out: Optional[Tensor] = None, row_stats: Optional[Tensor] = None) -> Tensor:
+    """The LLM.int8 inference forward with threshold > 0 for any row count, without a host synchronisation: A (fp16,
+    any rank, flattened over its leading dimensions) x CB [n, k] int8 -> fp16 [rows, n].
+
+      S          = the columns of A holding a value with |a| >= threshold
+      row_stats  = get_colrow_absmax(A, threshold=threshold)'s row half
+      CA         = double_quant(A, threshold=threshold)'s row half with every whole column of S zeroed
+      first      = igemmlt_dequant(CA, CB, row_stats, SCB, bias)                        (the routed int8 GEMM, fp16)
+      out[r, j]  = fp16(float(first[r, j]) + (SCB[j] / 127) * sum_{c in S, ascending} A[r, c] * CB[j, c])    (fp32)
+
+    cint8_outlier_quant_fp16 (a memset node and two launches), igemmlt_dequant, cint8_outlier_side_fp16 (one launch) on
+    a grow-only per-stream workspace: no COO, no tensor whose size depends on device data, so the call can be captured
+    into a HIP graph.  Deterministic.  Two roundings to fp16 (first, the sum) where the unfused composition has three
+    plus the weight columns'; without an outlier the bits are igemmlt_dequant(*int8_row_quant(A), CB, SCB, bias).
+    `row_stats` (fp32 [rows]), when given, receives the row statistics.  Shapes the kernels do not cover run the
+    unfused composition (_int8_linear_rows_unfused)."""
+    assert A.dtype == torch.float16 and CB.dtype == torch.int8
+    if not threshold > 0.0:
+        raise ValueError(f"int8_linear_outliers: threshold must be > 0, got {threshold}")
+    k = A.shape[-1]
+    m = A.numel() // k if k else 0
+    n = CB.shape[0]
+    assert CB.shape[1] == k
+    if bias is not None:
+        assert bias.dtype == torch.float16
+    if row_stats is not None:
+        assert row_stats.dtype == torch.float32 and row_stats.numel() == m and row_stats.is_contiguous()
+    A2 = A.reshape(m, k).contiguous()
+    if int8_linear_outliers_supported(m, n, k) and threshold != float("inf"):
+        CBc = CB.contiguous()
+        res = out if out is not None else torch.empty((m, n), dtype=torch.float16, device=A.device)
+        stats = row_stats if row_stats is not None else torch.empty((m,), dtype=torch.float32, device=A.device)
+        CA = torch.empty((m, k), dtype=torch.int8, device=A.device)
+        ws_bytes = int(lib.cint8_outlier_workspace_bytes(k))
+        ws = _outlier_workspace(A.device, ws_bytes)
+        prev_device = pre_call(A.device)
+        is_on_gpu([A2, CBc, SCB, res, stats, CA, ws])
+        rc = lib.cint8_outlier_quant_fp16(m, k, get_ptr(A2), ct.c_float(threshold), get_ptr(CA), get_ptr(stats),
+                                          get_ptr(ws), ws_bytes)
+        post_call(prev_device)
+        if rc == 1:
+            raise Exception("int8_linear_outliers ran into an error!")
+        if rc == 0:
+            igemmlt_dequant(CA, CBc, stats, SCB, bias=bias, out=res)
+            prev_device = pre_call(A.device)
+            rc = lib.cint8_outlier_side_fp16(m, n, k, get_ptr(A2), get_ptr(CBc), get_ptr(SCB), get_ptr(res), n,
+                                             get_ptr(ws))
+            post_call(prev_device)
+            if rc != 0:     # covered by the first call, so by this one: 2 cannot follow 0
+                raise Exception("int8_linear_outliers ran into an error!")
+            return res
+    return _int8_linear_rows_unfused(A2, CB, SCB, bias, threshold, out, row_stats)
 
 
 def igemm_rowmajor(A: Tensor, B: Tensor, out: Optional[Tensor] = None) -> Tensor:

@@ -259,11 +259,16 @@ class Linear8bitLt(nn.Linear):
 
     `fused_outlier_decode` (this backend's, off by default): an inference forward of 1..32 rows with threshold > 0
     runs as one launch (F.int8_linear_rows with the threshold), which rounds to fp16 once where the unfused path
-    rounds three times -- within a derived tolerance of it, not its bits."""
+    rounds three times -- within a derived tolerance of it, not its bits.
+
+    `fused_outlier_prefill` (this backend's, off by default): an inference forward of any row count with threshold > 0
+    finds the outlier columns on the device around the int8 GEMM (F.int8_linear_outliers): no host synchronisation, no
+    vendor GEMM, capturable into a HIP graph; two roundings to fp16, so within a derived tolerance of the unfused path,
+    not its bits.  With both flags set, 1..32 rows stay on the one-launch decode kernel."""
 
     def __init__(self, input_features: int, output_features: int, bias=True, has_fp16_weights=True,
                  memory_efficient_backward=False, threshold=0.0, index=None, device=None,
-                 fused_outlier_decode=False):
+                 fused_outlier_decode=False, fused_outlier_prefill=False):
         super().__init__(input_features, output_features, bias, device)
         assert not memory_efficient_backward, ("memory_efficient_backward is no longer required and the argument is "
                                                "deprecated in 0.37.0 and will be removed in 0.39.0")
@@ -273,6 +278,7 @@ class Linear8bitLt(nn.Linear):
         self.state.has_fp16_weights = has_fp16_weights
         self.state.memory_efficient_backward = memory_efficient_backward
         self.state.fused_outlier_decode = bool(fused_outlier_decode)
+        self.state.fused_outlier_prefill = bool(fused_outlier_prefill)
         if threshold > 0.0 and not has_fp16_weights:
             self.state.use_pool = True
         self.weight = Int8Params(self.weight.data, has_fp16_weights=has_fp16_weights, requires_grad=has_fp16_weights)

@@ -247,6 +247,24 @@ int cint8_linear_rows_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t*
 int cint8_linear_rows_outlier_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t* B, bnb_fp16* out,
                                    float* rowStats_out, int* outlier_cols_out, const float* colStats,
                                    const bnb_fp16* bias, float threshold, int lda, int ldb, int ldc);
+/* [additive] LLM.int8 prefill with a threshold and no host round trip (int8_outlier_prefill.hip): two calls around
+ * cigemmlt_row_dequant{,_ws}_fp16 that find the outlier columns on the device.  A [m, k] fp16, B [n, k] int8, both
+ * contiguous; threshold finite and > 0.  `ws` is a caller buffer of cint8_outlier_workspace_bytes(k) bytes, 16-B
+ * aligned: int count (the number of outlier columns), 12 unused bytes, one bit per column padded to 16 bytes, then
+ * int idx[k] (the outlier columns, ascending, count of them valid); the library allocates nothing.
+ *   cint8_outlier_quant_fp16: clears the mask on the stream, then two launches.  rowStats = cget_col_row_stats' row
+ *     half with the threshold; CA = cdouble_rowcol_quant's row half with every whole column that holds a value
+ *     |a| >= threshold zeroed; the list and its length in ws.
+ *   cint8_outlier_side_fp16: out (holding cigemmlt_row_dequant_fp16(CA, B, rowStats, colStats, bias), fp16) becomes
+ *     fp16(float(out[r, j]) + (colStats[j] / 127) * sum over the listed columns c, ascending, of A[r, c] * B[j, c]) in
+ *     fp32, one launch; nothing is written when the list is empty.  Deterministic: no float atomics.
+ * Both cover k % 8 == 0 with a 16-B aligned A.  Return 0 = launched (or m, n or k <= 0: nothing to do), 1 = error
+ * (cget_last_error), 2 = not covered: nothing launched, nothing written. */
+long long cint8_outlier_workspace_bytes(int k);
+int cint8_outlier_quant_fp16(int m, int k, const bnb_fp16* A, float threshold, char* CA, float* rowStats, void* ws,
+                             long long ws_bytes);
+int cint8_outlier_side_fp16(int m, int n, int k, const bnb_fp16* A, const int8_t* B, const float* colStats,
+                            bnb_fp16* out, int ldc, const void* ws);
 /* [additive, testing] which calls of cigemmlt_row_dequant{,_ws}_fp16 go to the decode kernel: 0 = auto (covered shapes
  * up to the measured row limit, unless cigemm_set_tile / cigemm_set_splitk force a route), 1 = wherever it covers,
  * -1 = never (the two direct entries then answer 2).  Returns the previous value. */

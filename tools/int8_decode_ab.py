@@ -24,6 +24,10 @@ with --outlier-cols C columns (default 8) given one value of magnitude 8..60 eac
 with the host, so both arms run eagerly between two device events (host time included, as a caller sees it); the
 fused arm is also replayed as a HIP graph ("fused_graph": its device time alone).  The two arms round differently (the
 fused one once): their largest difference is reported, not compared.  Writes profiles/int8_outlier_decode_ab.json.
+A second fused arm, "prefill", is the layer with fused_outlier_prefill on (int8_outlier_prefill.hip: the outlier columns
+found on the device around the int8 GEMM, any row count), eager and as a graph ("prefill_graph"); the decode arm runs
+only at 1..32 rows, where its kernel exists.  With every row count above 32 (--rows 64,256,1024,4096) the run is flag off
+against flag on for the prefill and writes profiles/int8_outlier_prefill_ab.json.
 
 Usage: python tools/int8_decode_ab.py [--rows 1,2,...] [--shapes 11008x4096,...] [--out FILE] [--window 0.2]
                                       [--threshold T [--outlier-cols C]]"""
@@ -97,11 +101,12 @@ def eager_window_ms(calls, iters):
     return s.elapsed_time(e)
 
 
-def make_layer(CB, SCB, bias, threshold, fused):
+def make_layer(CB, SCB, bias, threshold, fused, prefill=False):
     """A Linear8bitLt around an already quantised weight (CB, SCB are shared, not copied)."""
     from python_src_quants.nn import Int8Params, Linear8bitLt
     n, k = CB.shape
-    lin = Linear8bitLt(16, 16, bias=True, has_fp16_weights=False, threshold=threshold, fused_outlier_decode=fused)
+    lin = Linear8bitLt(16, 16, bias=True, has_fp16_weights=False, threshold=threshold, fused_outlier_decode=fused,
+                       fused_outlier_prefill=prefill)
     lin.in_features, lin.out_features = k, n
     lin.weight = Int8Params(CB, requires_grad=False, has_fp16_weights=False, CB=CB, SCB=SCB)
     lin.bias = torch.nn.Parameter(bias, requires_grad=False)
@@ -120,8 +125,8 @@ def main_outlier(args, rows_list, shapes):
             CBs = [torch.randint(-128, 128, (n, k), device=dev, dtype=torch.int8, generator=gen) for _ in range(copies)]
             SCB = torch.rand(n, device=dev, generator=gen) + 0.5
             bias = torch.randn(n, device=dev, generator=gen).half()
-            layers = {arm: [make_layer(CB, SCB, bias, args.threshold, arm == "fused") for CB in CBs]
-                      for arm in ("unfused", "fused")}
+            layers = {arm: [make_layer(CB, SCB, bias, args.threshold, arm == "fused", arm == "prefill") for CB in CBs]
+                      for arm in ("unfused", "fused", "prefill")}
             for rows in rows_list:
                 A = torch.randn(rows, k, device=dev, generator=gen).clamp_(-5, 5).half()
                 cols = torch.randperm(k, device=dev, generator=gen)[:args.outlier_cols]
@@ -136,37 +141,48 @@ def main_outlier(args, rows_list, shapes):
                         return run
                     return [call(lin) for lin in layers[arm]]
 
-                calls = {arm: arm_calls(arm) for arm in ("unfused", "fused")}
+                # the decode arm where its kernel exists: beyond 32 rows that layer is the unfused one
+                fused_arms = (["fused"] if rows <= F.IGEMV_MAX_ROWS else []) + ["prefill"]
+                calls = {arm: arm_calls(arm) for arm in ["unfused"] + fused_arms}
                 with torch.no_grad():
                     for arm in calls:                     # warm-up; both end on the last weight
                         for c in calls[arm]:
                             c()
                     torch.cuda.synchronize()
-                    diff = float((outs["unfused"].float() - outs["fused"].float()).abs().max())
+                    diff = {arm: float((outs["unfused"].float() - outs[arm].float()).abs().max()) for arm in fused_arms}
                     scale = float(outs["unfused"].float().abs().max())
-                    g = capture(calls["fused"])
                     iters = {}
                     for arm in calls:
                         ms = max(eager_window_ms(calls[arm], 1), 1e-3)
                         iters[arm] = max(2, int(args.window * 1e3 / ms) + 1)
-                    g_iters = max(3, int(args.window * 1e3 / max(window_ms(g, 3) / 3, 1e-3)) + 1)
-                    res = {"unfused": [], "fused": [], "fused_graph": []}
+                    res = {arm: [] for arm in list(calls) + [a + "_graph" for a in fused_arms]}
                     for _ in range(REPS):
                         for arm in calls:
                             res[arm].append(eager_window_ms(calls[arm], iters[arm]) * 1e3 / iters[arm] / copies)
-                        res["fused_graph"].append(window_ms(g, g_iters) * 1e3 / g_iters / copies)
-                    del g
+                        # captured anew after the eager windows: on an MI355X a graph of the prefill layer forward
+                        # (its tensors allocated in the graph's pool) that was instantiated BEFORE the unfused forward
+                        # ran replayed about ten times slower from then on (758 against 74 us per call at 1024 rows
+                        # on 4096 x 4096); a fresh capture does not (cause not found)
+                        for arm in fused_arms:
+                            g = capture(calls[arm])
+                            g_iters = max(3, int(args.window * 1e3 / max(window_ms(g, 3) / 3, 1e-3)) + 1)
+                            res[arm + "_graph"].append(window_ms(g, g_iters) * 1e3 / g_iters / copies)
+                            del g
                 row = {"n": n, "k": k, "rows": rows, "copies": copies, "threshold": args.threshold,
-                       "outlier_cols": args.outlier_cols, "max_abs_diff": diff, "max_abs_out": scale,
+                       "outlier_cols": args.outlier_cols, "max_abs_out": scale,
                        **{arm: summarise(ts) for arm, ts in res.items()}}
-                # the fused forward wins when even its slowest repetition beats the unfused forward's fastest
-                row["fused_wins_beyond_spread"] = row["fused"]["max_us"] < row["unfused"]["min_us"]
+                line = (f"{n:5d} x {k:5d} rows {rows:4d} thr {args.threshold:g} cols {args.outlier_cols}: unfused "
+                        f"{row['unfused']['median_us']:8.2f} us [{row['unfused']['min_us']:.2f}.."
+                        f"{row['unfused']['max_us']:.2f}]")
+                for arm in fused_arms:
+                    # a fused forward wins when even its slowest repetition beats the unfused forward's fastest
+                    row[arm + "_wins_beyond_spread"] = row[arm]["max_us"] < row["unfused"]["min_us"]
+                    row["max_abs_diff" if arm == "fused" else arm + "_max_abs_diff"] = diff[arm]
+                    line += (f"  {arm} {row[arm]['median_us']:8.2f} us [{row[arm]['min_us']:.2f}.."
+                             f"{row[arm]['max_us']:.2f}]  {arm} graph {row[arm + '_graph']['median_us']:8.2f} us  "
+                             f"max |diff| {diff[arm]:.4g} of {scale:.4g}")
                 table.append(row)
-                print(f"{n:5d} x {k:5d} rows {rows:2d} thr {args.threshold:g} cols {args.outlier_cols}: unfused "
-                      f"{row['unfused']['median_us']:8.2f} us [{row['unfused']['min_us']:.2f}.."
-                      f"{row['unfused']['max_us']:.2f}]  fused {row['fused']['median_us']:8.2f} us "
-                      f"[{row['fused']['min_us']:.2f}..{row['fused']['max_us']:.2f}]  fused graph "
-                      f"{row['fused_graph']['median_us']:8.2f} us  max |diff| {diff:.4g} of {scale:.4g}", flush=True)
+                print(line, flush=True)
             del CBs, layers
             torch.cuda.empty_cache()
     finally:
@@ -191,7 +207,10 @@ def main():
     rows_list = [int(r) for r in args.rows.split(",")]
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
     if args.out is None:
-        name = "int8_outlier_decode_ab.json" if args.threshold > 0.0 else "int8_decode_ab.json"
+        name = "int8_decode_ab.json"
+        if args.threshold > 0.0:
+            prefill_only = min(rows_list) > F.IGEMV_MAX_ROWS
+            name = "int8_outlier_prefill_ab.json" if prefill_only else "int8_outlier_decode_ab.json"
         args.out = os.path.join(ROOT, "profiles", name)
     if args.threshold > 0.0:
         return main_outlier(args, rows_list, shapes)
