@@ -27,6 +27,7 @@ enum DataType { GENERAL8BIT = 0, FP4 = 1, NF4 = 2 };
 
 // ---------------------------------------------------------------- runtime state
 hipStream_t current_stream();
+int device_cu_count();   // CUs of the current device, 256 without one (cached; gemv4bit.hip)
 void set_error(int code, const char* what);
 #define BNB_LAUNCH_CHECK(name)                                              \
   do {                                                                      \

@@ -173,50 +173,104 @@ static int splitk_factor(int m, int n, int k) {
   ks = std::min(ks, std::max(1, (k / G_BK) / 8));
   return std::max(1, std::min(ks, 16));
 }
+static long long splitk_bytes(int ks, int m, int n) { return ks > 1 ? (long long)ks * m * n * (long long)sizeof(float) : 0; }
 
-long long gemm_4bit_workspace_bytes(int m, int n, int k) {
-  const int ks = splitk_factor(m, n, k);
-  return std::max(ks > 1 ? (long long)ks * m * n * (long long)sizeof(float) : 0LL, skinny_workspace_bytes(m, n, k));
-}
-
-template <typename T>
-void gemm_4bit(int m, int n, int k, const T* A, const uint8_t* B, const float* absmax, const float* datatype, T* out,
-               int lda, int ldb, int ldc, int blocksize, float* ws = nullptr, long long ws_bytes = 0) {
-  if (m <= 0 || n <= 0) return;
-  if (k <= 0 || k % G_BK != 0 || lda % 8 != 0 || ldb % 16 != 0 || blocksize < 64 || blocksize % 32 != 0 ||
-      ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) {
-    set_error(1, "gemm_4bit: requires k % 64 == 0, lda % 8 == 0, ldb % 16 == 0, 16-B aligned A/B, blocksize >= 64");
-    return;
+// The plan's last stage, the tile kernels (plain statistics only).  Large problems: 256x256 tiles (split-K when the
+// tile grid is too small and a workspace is given); small: 128x128.
+static FtPlan tile_plan(const FtKnobs& kn, const FtProblem& p) {
+  FtPlan pl;
+  if (p.nested) return pl;
+  const int m = p.m, n = p.n, k = p.k;
+  if (k <= 0 || k % G_BK != 0 || !ft_aligned(p) || p.blocksize < 64 || p.blocksize % 32 != 0) {
+    pl.kernel = FT_BAD_ARGS;
+    return pl;
   }
-  // few tokens (<= 64, SK_MAX_TOKENS): the weight-streaming kernels (gemm4bit_skinny.hip, gemm4bit_wk.hip)
-  if (g_tile_override == 0) {
-    const SkStats st{absmax, nullptr, nullptr, nullptr, nullptr, 0, 0};
-    if (launch_gemm_4bit_skinny<T>(m, n, k, A, lda, B, ldb, st, blocksize, 0, datatype, out, ldc, ws, ws_bytes)) {
-      BNB_LAUNCH_CHECK("gemm_4bit");
-      return;
-    }
-  }
-  // m = out features (weight rows), n = tokens.  Large problems: 256x256 tiles (split-K when the
-  // tile grid is too small and a workspace is given); small: 128x128.
   const long long tiles256 = (long long)((m + 255) / 256) * ((n + 255) / 256);
-  const bool pow2_bs = (blocksize & (blocksize - 1)) == 0;
   int ks = splitk_factor(m, n, k);
-  if (ws == nullptr || ((uintptr_t)ws & 15) || (long long)ks * m * n * (long long)sizeof(float) > ws_bytes) ks = 1;
+  if (!p.ws_fits(splitk_bytes(ks, m, n))) ks = 1;
   // 256x256 (with split-K) when its grid fills the chip (>= 128 workgroups), and also when it still has at
   // least half the workgroups of the 128x128 grid, which then run the full K each (e.g. 512 features x
   // 256 tokens: 8 workgroups of 128x128 took 174 us where 2 x 16-way split 256x256 tiles take ~25)
   const long long tiles128 = (long long)((m + G_BN - 1) / G_BN) * ((n + G_BM - 1) / G_BM);
-  const bool use256 = pow2_bs && (g_tile_override == 256 ||
-                                  (g_tile_override != 128 && (m >= 256 || ks > 1) &&
-                                   (tiles256 * ks >= 128 || 2 * tiles256 * ks >= tiles128)));
-  if (use256) {
-    launch_gemm_4bit_256<T>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize, ws, ks);
-  } else {
-    const int tiles = ((m + G_BN - 1) / G_BN) * ((n + G_BM - 1) / G_BM);
-    hipLaunchKernelGGL((k_gemm_4bit<T>), dim3(tiles), dim3(G_THREADS), 0, current_stream(), m, n, k, A, B, absmax,
-                       datatype, out, lda, ldb, ldc, blocksize);
+  const bool use256 = ft_pow2(p.blocksize) &&
+                      (kn.tile_override == 256 || (kn.tile_override != 128 && (m >= 256 || ks > 1) &&
+                                                   (tiles256 * ks >= 128 || 2 * tiles256 * ks >= tiles128)));
+  pl.kernel = use256 ? FT_TILE256 : FT_TILE128;
+  pl.splits = use256 ? ks : 1;
+  pl.kchunk = k / G_BK;
+  pl.grid = (int)(use256 ? tiles256 * ks : tiles128);
+  pl.threads = use256 ? 512 : G_THREADS;
+  pl.waves = pl.threads / 64;
+  pl.reduce = pl.splits > 1;
+  pl.ws_bytes = splitk_bytes(pl.splits, m, n);
+  return pl;
+}
+
+// The stages in order; the first that takes the problem runs it.
+//   * the multi-row GEMV (only where the caller allows it): 2..4 rows that the whole-K MFMA kernel does not take;
+//   * 33..64 tokens: the split-K tile kernel that shares the token rows across 192 weight rows (gemm4bit_t64.hip);
+//   * then the whole-K MFMA kernel (gemm4bit_fewtok.hip) -- neither where a lab / test knob selects one of the older
+//     kernels (g_fewtoken_kernel, a forced split-K geometry);
+//   * the older weight-streaming kernels (gemm4bit_wk.hip, gemm4bit_skinny.hip);
+//   * the tile kernels, alone when g_tile_override names one.
+FtPlan fewtoken_plan(const FtKnobs& kn, const FtProblem& p) {
+  if (kn.tile_override == 0) {
+    const bool newer = kn.fewtoken_kernel == 0 && kn.skinny_cfg < 0;
+    const FtPlan ft = newer ? fewtok_plan(kn, p) : FtPlan{};
+    FtPlan pl;
+    if (p.allow_gemv && ft.kernel == FT_NONE && (pl = gemv_tok_plan(p)).kernel != FT_NONE) return pl;
+    if (newer && (pl = t64_plan(kn, p)).kernel != FT_NONE) return pl;
+    if (ft.kernel != FT_NONE) return ft;
+    if ((pl = wk_plan(kn, p)).kernel != FT_NONE) return pl;
+    if ((pl = skinny_plan(kn, p)).kernel != FT_NONE) return pl;
   }
-  BNB_LAUNCH_CHECK("gemm_4bit");
+  return tile_plan(kn, p);
+}
+
+// room for the partials of whichever kernel the plan picks, under any knob setting
+long long gemm_4bit_workspace_bytes(int m, int n, int k) {
+  return std::max({splitk_bytes(splitk_factor(m, n, k), m, n), skinny_workspace_bytes(m, n, k),
+                   t64_workspace_bytes(FtKnobs::load(), m, n, k)});
+}
+
+// 0 launched, 1 only a kernel that needs plain statistics is left (nothing launched), 2 error (recorded)
+template <typename T>
+static int gemm_4bit(int m, int n, int k, const FtArgs<T>& a, int lda, int ldb, int blocksize, int blocksize2,
+                     long long ws_bytes, bool allow_gemv) {
+  if (m <= 0 || n <= 0) return 0;
+  const FtProblem p = ft_problem(m, n, k, lda, ldb, blocksize, blocksize2, a, ws_bytes, allow_gemv);
+  const FtPlan pl = fewtoken_plan(FtKnobs::load(), p);
+  switch (pl.kernel) {
+    case FT_NONE: return 1;
+    case FT_BAD_ARGS:
+      set_error(1, "gemm_4bit: requires k % 64 == 0, lda % 8 == 0, ldb % 16 == 0, 16-B aligned A/B, blocksize >= 64");
+      return 2;
+    case FT_GEMV_TOK: gemv_tok_launch<T>(p, a, pl); break;
+    case FT_T64:
+    case FT_T64R: t64_launch<T>(p, a, pl); break;
+    case FT_FEWTOK: fewtok_launch<T>(p, a, pl); break;
+    case FT_WK: wk_launch<T>(p, a, pl); break;
+    case FT_SKINNY: launch_gemm_4bit_skinny<T>(p, a, pl); break;
+    case FT_TILE256:
+      launch_gemm_4bit_256<T>(m, n, k, a.A, a.B, a.absmax, a.code, a.out, lda, ldb, a.ldc, blocksize, a.ws, pl.splits);
+      break;
+    default:
+      hipLaunchKernelGGL((k_gemm_4bit<T>), dim3(pl.grid), dim3(G_THREADS), 0, current_stream(), m, n, k, a.A, a.B,
+                         a.absmax, a.code, a.out, lda, ldb, a.ldc, blocksize);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error((int)e, "gemm_4bit");
+    return 2;
+  }
+  return 0;
+}
+// plain statistics, no workspace, never the multi-row GEMV: the reference slots
+template <typename T>
+static void gemm_4bit_plain(int m, int n, int k, const T* A, const uint8_t* B, const float* absmax, const float* datatype,
+                            T* out, int lda, int ldb, int ldc, int blocksize) {
+  gemm_4bit<T>(m, n, k, FtArgs<T>{A, B, absmax, nullptr, nullptr, nullptr, nullptr, datatype, out, ldc, nullptr}, lda, ldb,
+               blocksize, 0, 0, false);
 }
 
 static __device__ float g_nf4_table[16] = {
@@ -241,43 +295,60 @@ extern "C" {
 void cgemm_4bit_inference(int m, int n, int k, fp16_t* A, unsigned char* B, float* absmax, fp16_t* out, int lda,
                           int ldb, int ldc, int blocksize) {
   BNB_RANGE("cgemm_4bit_inference");
-  gemm_4bit<fp16_t>(m, n, k, A, B, absmax, nf4_table_device(), out, lda, ldb, ldc, blocksize);
+  gemm_4bit_plain<fp16_t>(m, n, k, A, B, absmax, nf4_table_device(), out, lda, ldb, ldc, blocksize);
 }
 // bf16 sibling and table-driven variants (any 16-entry code: NF4/FP4).
 void cgemm_4bit_inference_bf16(int m, int n, int k, bf16_t* A, unsigned char* B, float* absmax, bf16_t* out, int lda,
                                int ldb, int ldc, int blocksize) {
   BNB_RANGE("cgemm_4bit_inference_bf16");
-  gemm_4bit<bf16_t>(m, n, k, A, B, absmax, nf4_table_device(), out, lda, ldb, ldc, blocksize);
+  gemm_4bit_plain<bf16_t>(m, n, k, A, B, absmax, nf4_table_device(), out, lda, ldb, ldc, blocksize);
 }
 void cgemm_4bit_inference_code_fp16(int m, int n, int k, fp16_t* A, unsigned char* B, float* absmax, float* datatype,
                                     fp16_t* out, int lda, int ldb, int ldc, int blocksize) {
   BNB_RANGE("cgemm_4bit_inference_code_fp16");
-  gemm_4bit<fp16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize);
+  gemm_4bit_plain<fp16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize);
 }
 void cgemm_4bit_inference_code_bf16(int m, int n, int k, bf16_t* A, unsigned char* B, float* absmax, float* datatype,
                                     bf16_t* out, int lda, int ldb, int ldc, int blocksize) {
   BNB_RANGE("cgemm_4bit_inference_code_bf16");
-  gemm_4bit<bf16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize);
+  gemm_4bit_plain<bf16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize);
 }
-// [additive] the same with a caller-owned fp32 workspace that enables split-K for small tile grids
-// (size it with cgemm_4bit_workspace_bytes; a smaller or NULL workspace just disables split-K).
-void cgemm_4bit_inference_code_ws_fp16(int m, int n, int k, fp16_t* A, unsigned char* B, float* absmax,
-                                       float* datatype, fp16_t* out, int lda, int ldb, int ldc, int blocksize,
-                                       float* workspace, long long workspace_bytes) {
-  BNB_RANGE("cgemm_4bit_inference_code_ws_fp16");
-  gemm_4bit<fp16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize, workspace, workspace_bytes);
+// [additive] the 4-bit GEMM of the Python layer, any number of activation rows, with a caller-owned fp32 workspace
+// (cgemm_4bit_workspace_bytes; a smaller or NULL workspace only rules out the kernels that split K): plain fp32
+// statistics (absmax_q = NULL) or compressed ones decoded in-kernel (absmax = NULL).  The one entry that may run 2..4
+// rows on the multi-row GEMV: up to gemv_rows of them (0: never).  Returns 0 when launched, 1 when only a kernel that needs plain statistics is left
+// (nothing launched: decode them and call again), 2 on error.
+int cgemm_4bit_inference_ws_fp16(int m, int ntok, int k, fp16_t* A, int lda, unsigned char* B, int ldb, float* absmax,
+                                 unsigned char* absmax_q, float* code2, float* absmax2, float* offset, float* datatype,
+                                 fp16_t* out, int ldc, int blocksize, int blocksize2, float* workspace,
+                                 long long workspace_bytes, int gemv_rows) {
+  BNB_RANGE("cgemm_4bit_inference_ws_fp16");
+  return gemm_4bit<fp16_t>(m, ntok, k, FtArgs<fp16_t>{A, B, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc, workspace},
+                           lda, ldb, blocksize, blocksize2, workspace_bytes, ntok <= gemv_rows);
 }
-void cgemm_4bit_inference_code_ws_bf16(int m, int n, int k, bf16_t* A, unsigned char* B, float* absmax,
-                                       float* datatype, bf16_t* out, int lda, int ldb, int ldc, int blocksize,
-                                       float* workspace, long long workspace_bytes) {
-  BNB_RANGE("cgemm_4bit_inference_code_ws_bf16");
-  gemm_4bit<bf16_t>(m, n, k, A, B, absmax, datatype, out, lda, ldb, ldc, blocksize, workspace, workspace_bytes);
+int cgemm_4bit_inference_ws_bf16(int m, int ntok, int k, bf16_t* A, int lda, unsigned char* B, int ldb, float* absmax,
+                                 unsigned char* absmax_q, float* code2, float* absmax2, float* offset, float* datatype,
+                                 bf16_t* out, int ldc, int blocksize, int blocksize2, float* workspace,
+                                 long long workspace_bytes, int gemv_rows) {
+  BNB_RANGE("cgemm_4bit_inference_ws_bf16");
+  return gemm_4bit<bf16_t>(m, ntok, k, FtArgs<bf16_t>{A, B, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc, workspace},
+                           lda, ldb, blocksize, blocksize2, workspace_bytes, ntok <= gemv_rows);
 }
 long long cgemm_4bit_workspace_bytes(int m, int n, int k) { return gemm_4bit_workspace_bytes(m, n, k); }
-
-}  // extern "C"
-
-extern "C" {
+// [additive, testing] the launch plan of cgemm_4bit_inference_ws_* for contiguous, aligned operands (lda = k,
+// ldb = k / 2) and a workspace of cgemm_4bit_workspace_bytes: out[0..15] = {kernel (FtKernel, gemm_common.hpp), grid,
+// threads, splits, kchunk, mt, rg, waves, s4, x8, cfg, lds, reduce launch follows, workspace bytes used (low, high 32
+// bits), 0}
+void cgemm_4bit_plan(int m, int ntok, int k, int blocksize, int blocksize2, int nested, int* out) {
+  BNB_RANGE("cgemm_4bit_plan");
+  const FtProblem p{m, ntok, k, k, k / 2, blocksize, blocksize2, nested != 0, true, true, true, true,
+                    gemm_4bit_workspace_bytes(m, ntok, k), true};
+  const FtPlan pl = fewtoken_plan(FtKnobs::load(), p);
+  const int v[16] = {pl.kernel, pl.grid, pl.threads, pl.splits, pl.kchunk, pl.mt, pl.rg, pl.waves, pl.s4, pl.x8, pl.cfg,
+                     pl.lds, pl.reduce ? 1 : 0, (int)(pl.ws_bytes & 0xFFFFFFFFLL), (int)(pl.ws_bytes >> 32), 0};
+  std::copy(v, v + 16, out);
+}
 // [additive, testing] force the tile kernel used by the 4-bit GEMM (0 = auto, 128 = 128x128 kernel)
 void cgemm_4bit_set_tile(int tile) { bnb::g_tile_override = tile; }
-}
+
+}  // extern "C"

@@ -459,17 +459,8 @@ k_gemm_4bit_fewtok(int N, int M, int K, const T* __restrict__ A, int lda, const 
 
 // 0 = auto, 1 = off, 2 = forced wherever it fits (A/B knob; tests); >= 16: lab ablations
 Knob<int> g_fewtok_mode{0};
-extern Knob<int> g_fewtoken_kernel;   // gemm4bit_wk.hip: != 0 selects one of the older few-token kernels
-int skinny_cfg_knob();          // gemm4bit_skinny.hip: >= 0 forces a split-K geometry (lab A/B)
 
-bool fewtok_applicable(int m, int n, int k, int lda, int ldb, int blocksize, const void* A, const void* B) {
-  return g_fewtok_mode != 1 && n >= 1 && n <= 32 && m >= 1 && k >= 64 && k % 64 == 0 && 2LL * ldb >= k &&
-         blocksize >= 64 && (blocksize & (blocksize - 1)) == 0 && lda % 8 == 0 && ldb % 16 == 0 &&
-         ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-         (long long)(n - 1) * lda * 2 + 2LL * k < 0x7FFFFFFFLL;
-}
-
-int fewtok_rows_groups(int m) {                           // RG: 16-row groups per workgroup (one workgroup per CU)
+static int fewtok_rows_groups(int m) {                    // RG: 16-row groups per workgroup (one workgroup per CU)
   const int cus = device_cu_count();
   return std::min(4, std::max(1, (m + 16 * cus - 1) / (16 * cus)));
 }
@@ -479,7 +470,7 @@ int fewtok_rows_groups(int m) {                           // RG: 16-row groups p
 // at 17..32 tokens only with >= 2 row groups per workgroup (one 16-row group re-reads each token fragment for too few
 // weights: 4096 x 11008 at 32 tokens 24.7 vs 21.8 us split-K); at 2..4 tokens not on the 4-wave 64-row form
 // (14336 x 4096 at 2 tokens 15.0 vs 12.0 us multi-row GEMV).
-bool fewtok_auto_takes(int m, int n, int k) {
+static bool fewtok_auto_takes(int m, int n) {
   const int cus = device_cu_count(), rg = fewtok_rows_groups(m);
   if (4 * ((m + 15) / 16) < 3 * cus) return false;
   if (n > 16 && rg < 2) return false;
@@ -487,85 +478,87 @@ bool fewtok_auto_takes(int m, int n, int k) {
   return true;
 }
 
-// m = out features (weight rows), n = tokens, k = in features.  False: not applicable (nothing launched).
-template <typename T>
-bool launch_gemm_4bit_fewtok(int m, int n, int k, const T* A, int lda, const uint8_t* B, int ldb, SkStats st,
-                             int blocksize, int blocksize2, const float* code, T* out, int ldc) {
-  if (!fewtok_applicable(m, n, k, lda, ldb, blocksize, A, B)) return false;
-  const bool nested = st.q8 != nullptr;
-  if (nested && (blocksize2 <= 0 || (blocksize2 & (blocksize2 - 1)))) return false;
-  if (g_fewtok_mode == 0 && !fewtok_auto_takes(m, n, k)) return false;
+#ifdef BNB_LAB
+// the ablation instances of the lab build (ABL values): 17..32 tokens, and <= 8 tokens, both on 48-row workgroups
+#define FT_LAB_MT2(X) X(128) X(129) X(130) X(132) X(135)
+#define FT_LAB_MT1(X) X(1) X(2) X(3) X(4) X(7) X(32) X(39) X(64) X(71) X(128) X(135) X(132) X(192) X(129)
+#define FT_LAB_IS(a) || v == a
+static bool ft_lab_mt2(int v) { return false FT_LAB_MT2(FT_LAB_IS); }
+static bool ft_lab_mt1(int v) { return false FT_LAB_MT1(FT_LAB_IS); }
+#endif
+
+FtPlan fewtok_plan(const FtKnobs& kn, const FtProblem& p) {
+  FtPlan pl;
+  const int m = p.m, n = p.n, k = p.k;
+  if (kn.fewtok_mode == 1 || n < 1 || n > 32 || m < 1 || k < 64 || k % 64 != 0 || 2LL * p.ldb < k || !ft_stream_ok(p) ||
+      (long long)(n - 1) * p.lda * 2 + 2LL * k >= 0x7FFFFFFFLL)
+    return pl;
+  if (kn.fewtok_mode == 0 && !fewtok_auto_takes(m, n)) return pl;
   // one workgroup per CU: RG 16-row groups each, as few as cover the rows in one round (11008 rows: 3 -> 230
   // workgroups); 8 waves (two per SIMD) where the LDS ring allows it, else 4
   const int rg = fewtok_rows_groups(m);
-  st.bs_shift = __builtin_ctz(blocksize);
-  st.bs2_shift = nested ? __builtin_ctz(blocksize2) : 0;
-  const dim3 grid((unsigned)((m + 16 * rg - 1) / (16 * rg)));
   // the 4-statistics-per-load form: blocksize 64, whole 4-block groups per row (K % 256 == 0, so every row's first
   // statistic is 4-aligned), a nested group of >= 4 blocks
-  const bool s4 = blocksize == 64 && k % 256 == 0 && (2LL * ldb) % 256 == 0 && (!nested || blocksize2 >= 4);
-  auto go = [&](auto kern, int waves) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, current_stream(), m, n, k, A, lda, B, ldb, st, code, out, ldc);
-  };
+  const bool s4 = p.blocksize == 64 && k % 256 == 0 && (2LL * p.ldb) % 256 == 0 && (!p.nested || p.blocksize2 >= 4);
+  pl.grid = (m + 16 * rg - 1) / (16 * rg);
+  pl.rg = rg;
+  pl.s4 = s4;
+  pl.mt = n <= 16 ? 1 : 2;
+  pl.x8 = pl.mt == 1 && n <= 8;
+  // (RG 3 at 17..32 tokens with per-block statistics: 4 waves, 8 would spill)
+  pl.waves = rg >= 4 || (rg == 3 && pl.mt == 2 && !s4) ? 4 : 8;
+  pl.kchunk = k / 64;
+  if (kn.fewtok_mode >= 16) {
 #ifndef BNB_LAB
-  if (g_fewtok_mode >= 16) return false;                    // (the ablation kernels exist in the lab build only)
+    return pl;                                              // (the ablation kernels exist in the lab build only)
 #else
-  if (g_fewtok_mode >= 16) {                                // lab ablations: nested, <= 8 tokens, 48-row workgroups
-    if (nested && s4 && rg == 3 && n > 16 && n <= 32) {     // (round 6: 17..32 tokens, timeline + ablations)
-      switch (g_fewtok_mode - 16) {
-        case 128: go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, 128>, 8); return true;
-        case 129: go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, 129>, 8); return true;
-        case 130: go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, 130>, 8); return true;
-        case 132: go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, 132>, 8); return true;
-        case 135: go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, 135>, 8); return true;
-        default: return false;
-      }
+    // lab ablations, nested statistics in the 4-per-load form: 17..32 tokens on 48-row workgroups (round 6: timeline +
+    // ablations), or <= 8 tokens on 48-row workgroups and the timeline of the 16-row form
+    pl.lab = kn.fewtok_mode - 16;
+    pl.waves = 8;
+    if (!p.nested || !s4) return pl;
+    if (rg == 3 && n > 16) {
+      if (!ft_lab_mt2(pl.lab)) return pl;
+    } else {
+      if (n > 8 || !(rg == 1 ? pl.lab == 128 : rg == 3 && ft_lab_mt1(pl.lab))) return pl;
     }
-    if (!nested || n > 8 || !s4) return false;
-    constexpr bool X8L = true;
-    if (rg == 1) {                                          // (timeline of the 16-row form)
-      if (g_fewtok_mode - 16 != 128) return false;
-      go(k_gemm_4bit_fewtok<T, 1, 1, true, true, 8, X8L, 128>, 8);
-      return true;
-    }
-    if (rg != 3) return false;
-    switch (g_fewtok_mode - 16) {
-      case 1: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 1>, 8); break;
-      case 2: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 2>, 8); break;
-      case 3: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 3>, 8); break;
-      case 4: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 4>, 8); break;
-      case 7: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 7>, 8); break;
-      case 32: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 32>, 8); break;
-      case 39: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 39>, 8); break;
-      case 64: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 64>, 8); break;
-      case 71: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 71>, 8); break;
-      case 128: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 128>, 8); break;
-      case 135: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 135>, 8); break;
-      case 132: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 132>, 8); break;
-      case 192: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 192>, 8); break;
-      case 129: go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, X8L, 129>, 8); break;
-      default: return false;
-    }
-    return true;
-  }
 #endif
-  const bool x8 = n <= 8;
+  }
+  pl.threads = 64 * pl.waves;
+  pl.kernel = FT_FEWTOK;
+  return pl;
+}
+
+template <typename T>
+void fewtok_launch(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  const SkStats st = ft_stats<SkStats>(p, a);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), 0, current_stream(), p.m, p.n, p.k, a.A, p.lda, a.B, p.ldb,
+                       st, a.code, a.out, a.ldc);
+  };
+#ifdef BNB_LAB
+#define FT_LAB_GO2(a) if (pl.mt == 2 && pl.lab == a) return go(k_gemm_4bit_fewtok<T, 3, 2, true, true, 8, false, a>);
+#define FT_LAB_GO1(a) if (pl.rg == 3 && pl.lab == a) return go(k_gemm_4bit_fewtok<T, 3, 1, true, true, 8, true, a>);
+  FT_LAB_MT2(FT_LAB_GO2)
+  FT_LAB_MT1(FT_LAB_GO1)
+  if (pl.lab != 0) return go(k_gemm_4bit_fewtok<T, 1, 1, true, true, 8, true, 128>);   // (timeline of the 16-row form)
+#endif
   auto by_rg = [&](auto mt_tag, auto nested_tag, auto s4_tag) {
     constexpr int MT = decltype(mt_tag)::value;
     constexpr bool NS = decltype(nested_tag)::value, S = decltype(s4_tag)::value;
     auto go_x8 = [&](auto rg_tag, auto waves_tag) {
       constexpr int R = decltype(rg_tag)::value, W = decltype(waves_tag)::value;
       if constexpr (MT == 1) {
-        if (x8) { go(k_gemm_4bit_fewtok<T, R, MT, NS, S, W, true>, W); return; }
+        if (pl.x8) { go(k_gemm_4bit_fewtok<T, R, MT, NS, S, W, true>); return; }
       }
-      go(k_gemm_4bit_fewtok<T, R, MT, NS, S, W, false>, W);
+      go(k_gemm_4bit_fewtok<T, R, MT, NS, S, W, false>);
     };
     using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>;
     using I3 = std::integral_constant<int, 3>;
     using I4 = std::integral_constant<int, 4>;
     using I8 = std::integral_constant<int, 8>;
-    switch (rg) {
+    switch (pl.rg) {
       case 1: go_x8(I1{}, I8{}); break;
       case 2: go_x8(I2{}, I8{}); break;
       case 3:   // (17..32 tokens with per-block statistics: 4 waves, 8 would spill)
@@ -576,22 +569,18 @@ bool launch_gemm_4bit_fewtok(int m, int n, int k, const T* A, int lda, const uin
     }
   };
   auto by_s4 = [&](auto mt_tag, auto nested_tag) {
-    if (s4) by_rg(mt_tag, nested_tag, std::true_type{});
+    if (pl.s4) by_rg(mt_tag, nested_tag, std::true_type{});
     else by_rg(mt_tag, nested_tag, std::false_type{});
   };
   auto by_tokens = [&](auto nested_tag) {
-    if (n <= 16) by_s4(std::integral_constant<int, 1>{}, nested_tag);
+    if (pl.mt == 1) by_s4(std::integral_constant<int, 1>{}, nested_tag);
     else by_s4(std::integral_constant<int, 2>{}, nested_tag);
   };
-  if (nested) by_tokens(std::true_type{});
+  if (p.nested) by_tokens(std::true_type{});
   else by_tokens(std::false_type{});
-  return true;
 }
-
-template bool launch_gemm_4bit_fewtok<bf16_t>(int, int, int, const bf16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                              const float*, bf16_t*, int);
-template bool launch_gemm_4bit_fewtok<fp16_t>(int, int, int, const fp16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                              const float*, fp16_t*, int);
+template void fewtok_launch<bf16_t>(const FtProblem&, const FtArgs<bf16_t>&, const FtPlan&);
+template void fewtok_launch<fp16_t>(const FtProblem&, const FtArgs<fp16_t>&, const FtPlan&);
 
 }  // namespace bnb
 
@@ -611,17 +600,5 @@ void cgemm_4bit_set_fewtok_mode(int mode) {
 #else
   bnb::g_fewtok_mode = (mode == 1 || mode == 2) ? mode : 0;
 #endif
-}
-// [additive] 1 when the 4-bit GEMM entry points run the whole-K few-token kernel for out features m, n activation rows,
-// in features k and this blocksize (the auto rule above, or the forced mode), else 0 -- the Python layer asks before
-// it sends 2..4 rows to the multi-row GEMV
-// (the launch's own conditions: a lab mode (>= 16), an older few-token kernel (g_fewtoken_kernel) or a forced split-K
-// geometry (g_skinny_cfg) each keep the launch off this kernel, so the answer is 0 for them too)
-int cgemm_4bit_fewtok_takes(int m, int n, int k, int blocksize) {
-  BNB_RANGE("cgemm_4bit_set_fewtok_mode");
-  if (bnb::g_fewtok_mode == 1 || bnb::g_fewtok_mode >= 16 || bnb::g_fewtoken_kernel != 0 || bnb::skinny_cfg_knob() >= 0 ||
-      n < 1 || n > 32 || k < 64 || k % 64 || blocksize < 64 || (blocksize & (blocksize - 1)))
-    return 0;
-  return (bnb::g_fewtok_mode >= 2 || bnb::fewtok_auto_takes(m, n, k)) ? 1 : 0;
 }
 }

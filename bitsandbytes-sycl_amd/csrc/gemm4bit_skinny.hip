@@ -271,12 +271,6 @@ template <int MT> constexpr int skinny_nb() { return MT == 1 ? 10 : (MT == 2 ? 5
 // 16-token MFMA tiles held: 1, 2, or 4 (33..64 rows)
 static int skinny_tiles(int n) { return n <= 16 ? 1 : (n <= 32 ? 2 : 4); }
 
-bool skinny_applicable(int m, int n, int k, int lda, int ldb, int blocksize, const void* A, const void* B) {
-  return n >= 1 && n <= SK_MAX_TOKENS && m >= 1 && k >= 128 && k % 128 == 0 && blocksize >= 64 &&
-         (blocksize & (blocksize - 1)) == 0 && lda % 8 == 0 && ldb % 16 == 0 && ((uintptr_t)A & 15) == 0 &&
-         ((uintptr_t)B & 15) == 0;
-}
-
 // Geometry (profiles/lab/r02_skinny_waves.txt).  The base form is 4 waves (64 weight rows) per workgroup with the NB
 // above.  At 33..64 rows a second form, 8 waves (128 weight rows sharing one LDS copy of the token rows) with twice the
 // blocks per split, halves the splits and so the fp32 partials the reduce re-reads: 4096 x 11008 at 64 rows 32.9 ->
@@ -284,20 +278,15 @@ bool skinny_applicable(int m, int n, int k, int lda, int ldb, int blocksize, con
 // workgroups is mostly empty (11008 x 4096: 516 workgroups on 256 CUs, 30.2 -> 36.8 us at 48 rows); it is taken when
 // that round is at least 70 % full.  At 1..32 rows the 8-wave forms lost everywhere (same NB: +1..3 us; 2 x NB: +5..14 us).
 // g_skinny_cfg (cgemm_4bit_set_skinny_config, lab A/B): -1 = that rule, 0 = base, 1 = 8 waves same NB, 2 = 8 waves 2 x NB.
-static Knob<int> g_skinny_cfg{-1};
-extern Knob<int> g_fewtoken_kernel;   // gemm4bit_wk.hip
-int skinny_cfg_knob() { return g_skinny_cfg; }
+Knob<int> g_skinny_cfg{-1};
 
 struct SkGeom {
   int cfg, waves, nb, splits;
 };
 
-int device_cu_count();   // CUs of the current device (cached; gemv4bit.hip)
-
-static SkGeom skinny_geometry(int m, int n, int k) {
+static SkGeom skinny_geometry(int cfg, int m, int n, int k) {
   const int mt = skinny_tiles(n), kb = k / 128;
   const int nb = mt == 1 ? skinny_nb<1>() : (mt == 2 ? skinny_nb<2>() : skinny_nb<4>());
-  int cfg = g_skinny_cfg;
   if (cfg < 0) {
     cfg = 0;
     if (mt == 4) {
@@ -309,53 +298,53 @@ static SkGeom skinny_geometry(int m, int n, int k) {
   const int nbw = cfg == 2 ? 2 * nb : nb;
   return SkGeom{cfg, cfg == 0 ? 4 : 8, nbw, (kb + nbw - 1) / nbw};
 }
+static long long skinny_partial_bytes(int splits, int m, int n) {
+  return splits > 1 ? (long long)splits * n * m * (long long)sizeof(float) : 0LL;
+}
+static bool skinny_shape_ok(int m, int n, int k) {
+  return n >= 1 && n <= SK_MAX_TOKENS && m >= 1 && k >= 128 && k % 128 == 0;
+}
 
 // workspace for any geometry: the base form has the most splits
 long long skinny_workspace_bytes(int m, int n, int k) {
-  if (n < 1 || n > SK_MAX_TOKENS || k < 128 || k % 128) return 0;
-  const int mt = skinny_tiles(n), nb = mt == 1 ? skinny_nb<1>() : (mt == 2 ? skinny_nb<2>() : skinny_nb<4>());
-  const int s = (k / 128 + nb - 1) / nb;
-  return std::max(s > 1 ? (long long)s * n * m * (long long)sizeof(float) : 0LL, t64_workspace_bytes(m, n, k));
+  return skinny_shape_ok(m, n, k) ? skinny_partial_bytes(skinny_geometry(0, m, n, k).splits, m, n) : 0;
 }
 
-// m = out features (weight rows), n = tokens, k = in features.  False: not applicable (shape, alignment
-// or workspace); the caller then uses the tile kernels.
+FtPlan skinny_plan(const FtKnobs& kn, const FtProblem& p) {
+  FtPlan pl;
+  if (!skinny_shape_ok(p.m, p.n, p.k) || !ft_stream_ok(p)) return pl;
+  const SkGeom geo = skinny_geometry(kn.skinny_cfg, p.m, p.n, p.k);
+  const long long bytes = skinny_partial_bytes(geo.splits, p.m, p.n);
+  if (geo.splits > 1 && !p.ws_fits(bytes)) return pl;
+  pl.kernel = FT_SKINNY;
+  pl.grid = ((p.m + 16 * geo.waves - 1) / (16 * geo.waves)) * geo.splits;
+  pl.waves = geo.waves;
+  pl.threads = 64 * geo.waves;
+  pl.splits = geo.splits;
+  pl.kchunk = geo.nb;
+  pl.mt = skinny_tiles(p.n);
+  pl.rg = geo.nb;
+  pl.cfg = geo.cfg;
+  pl.reduce = geo.splits > 1;
+  pl.ws_bytes = bytes;
+  return pl;
+}
+
 template <typename T>
-bool launch_gemm_4bit_skinny(int m, int n, int k, const T* A, int lda, const uint8_t* B, int ldb, SkStats st,
-                             int blocksize, int blocksize2, const float* code, T* out, int ldc, float* ws,
-                             long long ws_bytes) {
-  // 33..64 tokens: the split-K tile kernel that shares the token rows across 192 weight rows (gemm4bit_t64.hip); then
-  // the whole-K MFMA kernel (gemm4bit_fewtok.hip), unless a lab / test knob selects one of the older kernels
-  if (g_fewtoken_kernel == 0 && g_skinny_cfg < 0 &&
-      launch_gemm_4bit_t64<T>(m, n, k, A, lda, B, ldb, st, blocksize, blocksize2, code, out, ldc, ws, ws_bytes))
-    return true;
-  if (g_fewtoken_kernel == 0 && g_skinny_cfg < 0 &&
-      launch_gemm_4bit_fewtok<T>(m, n, k, A, lda, B, ldb, st, blocksize, blocksize2, code, out, ldc))
-    return true;
-  if (launch_gemm_4bit_wk<T>(m, n, k, A, lda, B, ldb, st, blocksize, blocksize2, code, out, ldc)) return true;
-  if (!skinny_applicable(m, n, k, lda, ldb, blocksize, A, B)) return false;
-  const bool nested = st.q8 != nullptr;
-  if (nested && (blocksize2 <= 0 || (blocksize2 & (blocksize2 - 1)))) return false;
-  const SkGeom geo = skinny_geometry(m, n, k);
-  const int s = geo.splits;
-  if (s > 1 && (ws == nullptr || ((uintptr_t)ws & 15) || (long long)s * n * m * (long long)sizeof(float) > ws_bytes))
-    return false;
-  st.bs_shift = __builtin_ctz(blocksize);
-  st.bs2_shift = nested ? __builtin_ctz(blocksize2) : 0;
-  const int waves = geo.waves;
-  const dim3 grid((unsigned)(((m + 16 * waves - 1) / (16 * waves)) * s));
+void launch_gemm_4bit_skinny(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  const SkStats st = ft_stats<SkStats>(p, a);
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, current_stream(), m, n, k, A, lda, B, ldb, st, code, ws, out,
-                       ldc, s);
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), 0, current_stream(), p.m, p.n, p.k, a.A, p.lda, a.B, p.ldb,
+                       st, a.code, a.ws, a.out, a.ldc, pl.splits);
   };
-  const int mt = skinny_tiles(n);
+  const int mt = pl.mt;
   auto dispatch = [&](auto nested_tag) {
     constexpr bool NS = decltype(nested_tag)::value;
-    if (geo.cfg == 0) {
+    if (pl.cfg == 0) {
       if (mt == 1) go(k_gemm_4bit_skinny<T, 1, skinny_nb<1>(), NS>);
       else if (mt == 2) go(k_gemm_4bit_skinny<T, 2, skinny_nb<2>(), NS>);
       else go(k_gemm_4bit_skinny<T, 4, skinny_nb<4>(), NS>);
-    } else if (geo.cfg == 1) {
+    } else if (pl.cfg == 1) {
       if (mt == 1) go(k_gemm_4bit_skinny<T, 1, skinny_nb<1>(), NS, 0, 8>);
       else if (mt == 2) go(k_gemm_4bit_skinny<T, 2, skinny_nb<2>(), NS, 0, 8>);
       else go(k_gemm_4bit_skinny<T, 4, skinny_nb<4>(), NS, 0, 8>);
@@ -365,10 +354,9 @@ bool launch_gemm_4bit_skinny(int m, int n, int k, const T* A, int lda, const uin
       else go(k_gemm_4bit_skinny<T, 4, 2 * skinny_nb<4>(), NS, 0, 8>);
     }
   };
-  if (nested) dispatch(std::true_type{});
+  if (p.nested) dispatch(std::true_type{});
   else dispatch(std::false_type{});
-  if (s > 1) launch_splitk_rows_reduce<T>(ws, s, n, m, out, ldc);
-  return true;
+  if (pl.reduce) launch_splitk_rows_reduce<T>(a.ws, pl.splits, p.n, p.m, a.out, a.ldc);
 }
 
 // out[t, n] = T(sum_s ws[s][t][n]) for any producer of row-major fp32 split partials (the split-K of k_hgemm too)
@@ -386,49 +374,13 @@ void launch_splitk_rows_reduce(const float* ws, int nsplit, int rows, int cols, 
 template void launch_splitk_rows_reduce<bf16_t>(const float*, int, int, int, bf16_t*, int);
 template void launch_splitk_rows_reduce<fp16_t>(const float*, int, int, int, fp16_t*, int);
 
-template bool launch_gemm_4bit_skinny<bf16_t>(int, int, int, const bf16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                              const float*, bf16_t*, int, float*, long long);
-template bool launch_gemm_4bit_skinny<fp16_t>(int, int, int, const fp16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                              const float*, fp16_t*, int, float*, long long);
+template void launch_gemm_4bit_skinny<bf16_t>(const FtProblem&, const FtArgs<bf16_t>&, const FtPlan&);
+template void launch_gemm_4bit_skinny<fp16_t>(const FtProblem&, const FtArgs<fp16_t>&, const FtPlan&);
 
 }  // namespace bnb
 
-using namespace bnb;
-
 extern "C" {
-
 // [lab, not in the header] A/B knob of the few-token split-K kernel's geometry: -1 = the measured rule (default),
 // 0 / 1 / 2 = forced (see g_skinny_cfg)
 void cgemm_4bit_set_skinny_config(int cfg) { bnb::g_skinny_cfg = cfg; }
-
-// [additive] few-token 4-bit GEMM with compressed statistics decoded in-kernel (one launch instead of
-// the absmax decode + GEMM; functional.py:1346-1350 order).  Returns 0 when launched, 1 when the shape,
-// alignment or workspace (cgemm_4bit_workspace_bytes) does not fit this kernel.
-int cgemm_4bit_inference_nested_ws_bf16(int m, int n, int k, bf16_t* A, unsigned char* B, unsigned char* absmax_q,
-                                        float* code2, float* absmax2, float* offset, float* datatype, bf16_t* out,
-                                        int lda, int ldb, int ldc, int blocksize, int blocksize2, float* workspace,
-                                        long long workspace_bytes) {
-  BNB_RANGE("cgemm_4bit_inference_nested_ws_bf16");
-  SkStats st{nullptr, absmax_q, code2, absmax2, offset, 0, 0};
-  if (m <= 0 || n <= 0) return 0;
-  if (!launch_gemm_4bit_skinny<bf16_t>(m, n, k, A, lda, B, ldb, st, blocksize, blocksize2, datatype, out, ldc,
-                                       workspace, workspace_bytes))
-    return 1;
-  BNB_LAUNCH_CHECK("gemm_4bit_nested");
-  return 0;
 }
-int cgemm_4bit_inference_nested_ws_fp16(int m, int n, int k, fp16_t* A, unsigned char* B, unsigned char* absmax_q,
-                                        float* code2, float* absmax2, float* offset, float* datatype, fp16_t* out,
-                                        int lda, int ldb, int ldc, int blocksize, int blocksize2, float* workspace,
-                                        long long workspace_bytes) {
-  BNB_RANGE("cgemm_4bit_inference_nested_ws_fp16");
-  SkStats st{nullptr, absmax_q, code2, absmax2, offset, 0, 0};
-  if (m <= 0 || n <= 0) return 0;
-  if (!launch_gemm_4bit_skinny<fp16_t>(m, n, k, A, lda, B, ldb, st, blocksize, blocksize2, datatype, out, ldc,
-                                       workspace, workspace_bytes))
-    return 1;
-  BNB_LAUNCH_CHECK("gemm_4bit_nested");
-  return 0;
-}
-
-}  // extern "C"

@@ -787,11 +787,81 @@ Knob<int> g_t64_pstore{2};
 // unsplit 28672 x 8192 at 64 rows 76.4 -> 72.0 us, profiles/lab/r05_t64r_ab.txt)
 Knob<int> g_t64_kp{0};
 
+struct T64Geom {
+  int row_tiles, ksplit, kc;
+};
+static T64Geom t64_geometry(int forced_ks, int m, int k) {
+  const int rt = (m + T64_ROWS - 1) / T64_ROWS, ngr = k / 256;
+  int ks = std::max(1, std::min(ngr, device_cu_count() / std::max(1, rt)));   // one round of workgroups on the CUs
+  if (forced_ks > 0) ks = std::min(ngr, forced_ks);
+  const int kc = (ngr + ks - 1) / ks;
+  ks = (ngr + kc - 1) / kc;
+  return {rt, ks, kc};
+}
+static long long t64_partial_bytes(int ksplit, int m, int n) {
+  return ksplit > 1 ? (long long)ksplit * n * m * (long long)sizeof(float) : 0;
+}
+
+// the register-fed form (k_gemm_4bit_t64r): 1 (default) = off, 2 = wherever the 33..64-token kernel applies, 0 = auto
+// (where its row tiles alone fill >= 3/4 of the CUs).  Off by default: measured 1.4-2.8x slower than the LDS-DMA form +
+// reduce on every shape, growing with the token rows -- every workgroup pulls all 64 x K token values through its
+// vector-memory path, 4x the LDS-DMA form's 64 x K/4 (profiles/lab/r05_t64r_ab.txt; a rotated group order per workgroup,
+// against L2-channel camping of the 16 same-channel token rows of one load, changed nothing)
+Knob<int> g_t64r{1};
+static bool t64r_route(const FtKnobs& kn, const FtProblem& p) {
+  if (kn.t64r == 1 || kn.t64_mode >= 15) return false;       // (the LDS-DMA form's labs keep their kernel)
+  if (!p.stats16) return false;
+  if (kn.t64r == 2) return true;
+  return 4LL * ((p.m + T64R_ROWS - 1) / T64R_ROWS) >= 3LL * device_cu_count();
+}
+
+long long t64_workspace_bytes(const FtKnobs& kn, int m, int n, int k) {
+  if (n < 1 || n > 64 || k < 256 || k % 256) return 0;
+  return t64_partial_bytes(t64_geometry(kn.t64_ks, m, k).ksplit, m, n);
+}
+
+FtPlan t64_plan(const FtKnobs& kn, const FtProblem& p) {
+  FtPlan pl;
+  const int m = p.m, n = p.n, k = p.k;
+  if (kn.t64_mode == 1) return pl;
+  if (n < 1 || n > 64 || ((kn.t64_mode == 0 || kn.t64_mode >= 16) && n < 33)) return pl;
+  if (!(m >= 1 && k >= 256 && k % 256 == 0 && p.blocksize == 64 && 2LL * p.ldb >= k && p.ldb % 128 == 0 &&
+        ft_aligned(p) && (!p.nested || (p.blocksize2 >= 4 && ft_pow2(p.blocksize2))) &&
+        (long long)(m - 1) * p.ldb + k / 2 < 0xFFFFFFFFLL && (long long)(n - 1) * p.lda * 2 + 2LL * k < 0x7FFFFFFFLL))
+    return pl;
+  if (t64r_route(kn, p)) {
+    pl.kernel = FT_T64R;
+    pl.grid = (m + T64R_ROWS - 1) / T64R_ROWS;
+    pl.threads = 256;
+    pl.waves = 4;
+    pl.kchunk = (k / 256 + 3) / 4;
+    return pl;
+  }
+  const T64Geom geo = t64_geometry(kn.t64_ks, m, k);
+  const long long bytes = t64_partial_bytes(geo.ksplit, m, n);
+  if (geo.ksplit > 1 && !p.ws_fits(bytes)) return pl;
+  pl.kernel = FT_T64;
+  pl.grid = geo.row_tiles * geo.ksplit;
+  pl.splits = geo.ksplit;
+  pl.kchunk = geo.kc;
+  pl.ws_bytes = bytes;
+  pl.pstore = bytes <= 0x7FFFFFFFLL ? kn.t64_pstore : 0;
+  // the split partials meet in the kernel (t64_tickets) or in a reduce launch; lab mode 15 leaves them unsummed
+  const bool sum = geo.ksplit > 1 && kn.t64_mode != 15;
+  pl.combine = sum && kn.t64_combine && geo.row_tiles <= T64_MAX_TILES && bytes <= 0x7FFFFFFFLL;
+  pl.reduce = sum && !pl.combine;
+#ifdef BNB_LAB
+  if (kn.t64_mode >= 16 && p.nested) pl.lab = kn.t64_mode;  // lab ablations (nested only), on the 4-wave kernel
+#endif
+  pl.waves = pl.lab == 0 && (kn.t64_kp == 2 || (kn.t64_kp == 0 && (n <= 48 || geo.ksplit == 1))) ? 8 : 4;
+  pl.threads = 64 * pl.waves;
+  return pl;
+}
+
 // this launch's ticket set on the current device (nullptr: use the reduce launch).  Never during HIP-graph capture: a
 // captured launch would bake one ticket set into the graph, and its replays could then share counters with eager
 // launches handed the same set -- captured work always takes the reduce launch.
-static uint32_t* t64_tickets(int row_tiles, long long partial_bytes) {
-  if (!g_t64_combine || row_tiles > T64_MAX_TILES || partial_bytes > 0x7FFFFFFFLL) return nullptr;
+static uint32_t* t64_tickets() {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(current_stream(), &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
     (void)hipGetLastError();
@@ -809,129 +879,47 @@ static uint32_t* t64_tickets(int row_tiles, long long partial_bytes) {
   return base[dev] + (next[dev]++ % T64_TICKET_SETS) * T64_MAX_TILES;
 }
 
-struct T64Geom {
-  int row_tiles, ksplit, kc;
-};
-static T64Geom t64_geometry(int m, int k) {
-  const int rt = (m + T64_ROWS - 1) / T64_ROWS, ngr = k / 256;
-  int cus = device_cu_count();
-  if (cus <= 0) cus = 256;
-  int ks = std::max(1, std::min(ngr, cus / std::max(1, rt)));   // one round of workgroups on the CUs
-  if (g_t64_ks > 0) ks = std::min(ngr, g_t64_ks.load());
-  const int kc = (ngr + ks - 1) / ks;
-  ks = (ngr + kc - 1) / kc;
-  return {rt, ks, kc};
-}
-
-bool t64_applicable(int m, int n, int k, int lda, int ldb, int blocksize, int blocksize2, bool nested, const void* A,
-                    const void* B) {
-  if (g_t64_mode == 1) return false;
-  if (n < 1 || n > 64 || ((g_t64_mode == 0 || g_t64_mode >= 16) && n < 33)) return false;
-  return m >= 1 && k >= 256 && k % 256 == 0 && blocksize == 64 && 2LL * ldb >= k && ldb % 128 == 0 &&
-         lda % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 &&
-         (!nested || (blocksize2 >= 4 && (blocksize2 & (blocksize2 - 1)) == 0)) &&
-         (long long)(m - 1) * ldb + k / 2 < 0xFFFFFFFFLL && (long long)(n - 1) * lda * 2 + 2LL * k < 0x7FFFFFFFLL;
-}
-
-// the register-fed form (k_gemm_4bit_t64r): 1 (default) = off, 2 = wherever the 33..64-token kernel applies, 0 = auto
-// (where its row tiles alone fill >= 3/4 of the CUs).  Off by default: measured 1.4-2.8x slower than the LDS-DMA form +
-// reduce on every shape, growing with the token rows -- every workgroup pulls all 64 x K token values through its
-// vector-memory path, 4x the LDS-DMA form's 64 x K/4 (profiles/lab/r05_t64r_ab.txt; a rotated group order per workgroup,
-// against L2-channel camping of the 16 same-channel token rows of one load, changed nothing)
-Knob<int> g_t64r{1};
-static bool t64r_route(int m, int k, const SkStats& st, bool nested) {
-  if (g_t64r == 1 || g_t64_mode >= 15) return false;         // (the LDS-DMA form's labs keep their kernel)
-  if (nested ? ((uintptr_t)st.q8 & 3) != 0 : ((uintptr_t)st.absmax & 15) != 0) return false;
-  if (g_t64r == 2) return true;
-  int cus = device_cu_count();
-  if (cus <= 0) cus = 256;
-  return 4LL * ((m + T64R_ROWS - 1) / T64R_ROWS) >= 3LL * cus;
-}
-
-long long t64_workspace_bytes(int m, int n, int k) {
-  if (n < 1 || n > 64 || k < 256 || k % 256) return 0;
-  const T64Geom geo = t64_geometry(m, k);
-  return geo.ksplit > 1 ? (long long)geo.ksplit * n * m * (long long)sizeof(float) : 0;
-}
-
-// m = out features (weight rows), n = tokens, k = in features.  False: not applicable (nothing launched).
 template <typename T>
-bool launch_gemm_4bit_t64(int m, int n, int k, const T* A, int lda, const uint8_t* B, int ldb, SkStats st,
-                          int blocksize, int blocksize2, const float* code, T* out, int ldc, float* ws,
-                          long long ws_bytes) {
-  const bool nested = st.q8 != nullptr;
-  if (!t64_applicable(m, n, k, lda, ldb, blocksize, blocksize2, nested, A, B)) return false;
-  if (t64r_route(m, k, st, nested)) {
-    const int kc = (k / 256 + 3) / 4;
-    const dim3 grid((unsigned)((m + T64R_ROWS - 1) / T64R_ROWS));
-    st.bs_shift = 6;
-    st.bs2_shift = nested ? __builtin_ctz(blocksize2) : 0;
+void t64_launch(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  const SkStats st = ft_stats<SkStats>(p, a);
+  const dim3 grid((unsigned)pl.grid);
+  if (pl.kernel == FT_T64R) {
     auto go = [&](auto kern) {
-      hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(), m, n, k, A, lda, B, ldb, st, code, out, ldc, kc);
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, current_stream(), p.m, p.n, p.k, a.A, p.lda, a.B, p.ldb, st, a.code,
+                         a.out, a.ldc, pl.kchunk);
     };
-    if (nested) go(k_gemm_4bit_t64r<T, true>);
+    if (p.nested) go(k_gemm_4bit_t64r<T, true>);
     else go(k_gemm_4bit_t64r<T, false>);
-    return true;
+    return;
   }
-  const T64Geom geo = t64_geometry(m, k);
-  if (geo.ksplit > 1 &&
-      (ws == nullptr || ((uintptr_t)ws & 15) || (long long)geo.ksplit * n * m * (long long)sizeof(float) > ws_bytes))
-    return false;
-  st.bs_shift = 6;
-  st.bs2_shift = nested ? __builtin_ctz(blocksize2) : 0;
-  const dim3 grid((unsigned)(geo.row_tiles * geo.ksplit));
-  uint32_t* tickets = geo.ksplit > 1 && g_t64_mode != 15 ? t64_tickets(geo.row_tiles, (long long)geo.ksplit * n * m * 4) : nullptr;
-  const int pstore = (long long)geo.ksplit * n * m * 4 <= 0x7FFFFFFFLL ? g_t64_pstore.load() : 0;
-  auto lab = [&](auto kern) {
-    hipLaunchKernelGGL(kern, grid, dim3(T64_THREADS), 0, current_stream(), m, n, k, A, lda, B, ldb, st, code, out, ldc, ws,
-                       geo.ksplit, geo.kc, tickets, pstore);
+  uint32_t* tickets = pl.combine ? t64_tickets() : nullptr;
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(pl.threads), 0, current_stream(), p.m, p.n, p.k, a.A, p.lda, a.B, p.ldb, st, a.code,
+                       a.out, a.ldc, a.ws, pl.splits, pl.kchunk, tickets, pl.pstore);
+  };
+  auto reduce = [&] {
+    if (pl.reduce || (pl.combine && tickets == nullptr)) launch_splitk_rows_reduce<T>(a.ws, pl.splits, p.n, p.m, a.out, a.ldc);
   };
 #ifdef BNB_LAB
-  if (g_t64_mode >= 16 && nested) {                          // lab ablations (nested bf16 / fp16 only)
-    switch (g_t64_mode - 16) {
-      case 1: lab(k_gemm_4bit_t64<T, true, 1>); break;
-      case 2: lab(k_gemm_4bit_t64<T, true, 2>); break;
-      case 4: lab(k_gemm_4bit_t64<T, true, 4>); break;
-      case 6: lab(k_gemm_4bit_t64<T, true, 6>); break;
-      case 8: lab(k_gemm_4bit_t64<T, true, 8>); break;
-      case 16: lab(k_gemm_4bit_t64<T, true, 16>); break;
-      case 24: lab(k_gemm_4bit_t64<T, true, 24>); break;
-      case 30: lab(k_gemm_4bit_t64<T, true, 30>); break;
-      case 32: lab(k_gemm_4bit_t64<T, true, 32>); break;
-      case 15: lab(k_gemm_4bit_t64<T, true>); break;
-      case 64: lab(k_gemm_4bit_t64<T, true, 64>); break;
-      case 128: lab(k_gemm_4bit_t64<T, true, 128>); break;
-      case 256: lab(k_gemm_4bit_t64<T, true, 256>); break;
-      case 512: lab(k_gemm_4bit_t64<T, true, 512>); break;
-      case 30 + 32 + 64 + 128 + 256: lab(k_gemm_4bit_t64<T, true, 30 + 32 + 64 + 128 + 256>); break;
-      default: lab(k_gemm_4bit_t64<T, true>); break;
-    }
+  if (pl.lab != 0) {
+#define T64_LAB(X) X(1) X(2) X(4) X(6) X(8) X(16) X(24) X(30) X(32) X(64) X(128) X(256) X(512) X(30 + 32 + 64 + 128 + 256)
+#define T64_LAB_GO(a) if (pl.lab - 16 == (a)) return go(k_gemm_4bit_t64<T, true, (a)>), reduce();
+    T64_LAB(T64_LAB_GO)
+    go(k_gemm_4bit_t64<T, true>);
   } else
-#else
-  (void)lab;
 #endif
-  if (g_t64_kp == 2 || (g_t64_kp == 0 && (n <= 48 || geo.ksplit == 1))) {
-    if (nested)
-      hipLaunchKernelGGL((k_gemm_4bit_t64<T, true, 0, 2>), grid, dim3(2 * T64_THREADS), 0, current_stream(), m, n, k, A,
-                         lda, B, ldb, st, code, out, ldc, ws, geo.ksplit, geo.kc, tickets, pstore);
-    else
-      hipLaunchKernelGGL((k_gemm_4bit_t64<T, false, 0, 2>), grid, dim3(2 * T64_THREADS), 0, current_stream(), m, n, k, A,
-                         lda, B, ldb, st, code, out, ldc, ws, geo.ksplit, geo.kc, tickets, pstore);
-  } else if (nested)
-    hipLaunchKernelGGL((k_gemm_4bit_t64<T, true>), grid, dim3(T64_THREADS), 0, current_stream(), m, n, k, A, lda, B, ldb,
-                       st, code, out, ldc, ws, geo.ksplit, geo.kc, tickets, pstore);
-  else
-    hipLaunchKernelGGL((k_gemm_4bit_t64<T, false>), grid, dim3(T64_THREADS), 0, current_stream(), m, n, k, A, lda, B,
-                       ldb, st, code, out, ldc, ws, geo.ksplit, geo.kc, tickets, pstore);
-  if (geo.ksplit > 1 && g_t64_mode != 15 && tickets == nullptr)
-    launch_splitk_rows_reduce<T>(ws, geo.ksplit, n, m, out, ldc);
-  return true;
+  if (pl.waves == 8) {
+    if (p.nested) go(k_gemm_4bit_t64<T, true, 0, 2>);
+    else go(k_gemm_4bit_t64<T, false, 0, 2>);
+  } else if (p.nested) {
+    go(k_gemm_4bit_t64<T, true>);
+  } else {
+    go(k_gemm_4bit_t64<T, false>);
+  }
+  reduce();
 }
-
-template bool launch_gemm_4bit_t64<bf16_t>(int, int, int, const bf16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                           const float*, bf16_t*, int, float*, long long);
-template bool launch_gemm_4bit_t64<fp16_t>(int, int, int, const fp16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                           const float*, fp16_t*, int, float*, long long);
+template void t64_launch<bf16_t>(const FtProblem&, const FtArgs<bf16_t>&, const FtPlan&);
+template void t64_launch<fp16_t>(const FtProblem&, const FtArgs<fp16_t>&, const FtPlan&);
 
 }  // namespace bnb
 

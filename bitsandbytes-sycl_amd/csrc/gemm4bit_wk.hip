@@ -152,28 +152,16 @@ k_gemm_4bit_wk(int N, int M, int K, const T* __restrict__ A, int lda, const uint
   }
 }
 
-int device_cu_count();      // CUs of the current device (cached; gemv4bit.hip)
 // 0 = auto (this kernel at <= WK_MAX_TOKENS tokens on narrow weights, else the split-K kernel), 1 = the split-K
 // skinny kernel only, 2 = this kernel for every shape it fits (A/B knob; tests)
 Knob<int> g_fewtoken_kernel{0};
 constexpr int WK_MAX_TOKENS = 6;
 
-bool wk_applicable(int m, int n, int k, int lda, int ldb, int blocksize, const void* A, const void* B) {
-  return g_fewtoken_kernel != 1 && n >= 1 && n <= 32 && m >= 1 && k >= 128 && k % 128 == 0 && blocksize >= 64 &&
-         (blocksize & (blocksize - 1)) == 0 && lda % 8 == 0 && ldb % 16 == 0 && ((uintptr_t)A & 15) == 0 &&
-         ((uintptr_t)B & 15) == 0;
-}
-
-// m = out features (weight rows), n = tokens, k = in features.  False: not applicable.
-template <typename T>
-bool launch_gemm_4bit_wk(int m, int n, int k, const T* A, int lda, const uint8_t* B, int ldb, SkStats st,
-                         int blocksize, int blocksize2, const float* code, T* out, int ldc) {
-  if (!wk_applicable(m, n, k, lda, ldb, blocksize, A, B)) return false;
-  const bool nested = st.q8 != nullptr;
-  if (nested && (blocksize2 <= 0 || (blocksize2 & (blocksize2 - 1)))) return false;
-  st.bs_shift = __builtin_ctz(blocksize);
-  st.bs2_shift = nested ? __builtin_ctz(blocksize2) : 0;
-  const int tiles = (m + 15) / 16;
+FtPlan wk_plan(const FtKnobs& kn, const FtProblem& p) {
+  FtPlan pl;
+  if (kn.fewtoken_kernel == 1 || p.n < 1 || p.n > 32 || p.m < 1 || p.k < 128 || p.k % 128 != 0 || !ft_stream_ok(p))
+    return pl;
+  const int tiles = (p.m + 15) / 16;
   // Where it is used (tools/fewtoken_ab.py, profiles/lab/r02_fewtoken_whole_k.txt): every workgroup reads the
   // token rows of all of K from L2, 16 weight rows per read, so the activation traffic grows with the tokens and
   // the split-K kernel (64 weight rows share one LDS copy) wins from ~8 tokens on, and on wide weights (>= 2 row
@@ -182,28 +170,36 @@ bool launch_gemm_4bit_wk(int m, int n, int k, const T* A, int lda, const uint8_t
   // it for every 1..32-token shape (tests, A/B).
   // Not on long K or on very narrow weights either (1024 x 28672 at 2..4 rows 26-29 vs 15.7 us split-K; 128 x 8192
   // 9.6 vs 8.8 us: profiles/lab/r02_gemv_wide.txt): every workgroup re-reads the token rows of all of K from L2.
-  const bool forced = g_fewtoken_kernel == 2;
-  if (!forced && (n > WK_MAX_TOKENS || tiles >= 2 * device_cu_count() || tiles < 64 || k > 16384)) return false;
   const bool wide = tiles >= 2 * device_cu_count();
-  const dim3 grid((unsigned)tiles);
-  auto go = [&](auto kern, int waves) {
-    hipLaunchKernelGGL(kern, grid, dim3(64 * waves), 0, current_stream(), m, n, k, A, lda, B, ldb, st, code, out, ldc);
-  };
-  const bool mt1 = n <= 16;
-  if (nested) {
-    if (mt1) wide ? go(k_gemm_4bit_wk<T, 1, 4, 4, true>, 4) : go(k_gemm_4bit_wk<T, 1, 8, 4, true>, 8);
-    else wide ? go(k_gemm_4bit_wk<T, 2, 4, 3, true>, 4) : go(k_gemm_4bit_wk<T, 2, 8, 3, true>, 8);
-  } else {
-    if (mt1) wide ? go(k_gemm_4bit_wk<T, 1, 4, 4, false>, 4) : go(k_gemm_4bit_wk<T, 1, 8, 4, false>, 8);
-    else wide ? go(k_gemm_4bit_wk<T, 2, 4, 3, false>, 4) : go(k_gemm_4bit_wk<T, 2, 8, 3, false>, 8);
-  }
-  return true;
+  if (kn.fewtoken_kernel != 2 && (p.n > WK_MAX_TOKENS || wide || tiles < 64 || p.k > 16384)) return pl;
+  pl.kernel = FT_WK;
+  pl.grid = tiles;
+  pl.waves = wide ? 4 : 8;
+  pl.threads = 64 * pl.waves;
+  pl.mt = p.n <= 16 ? 1 : 2;
+  pl.rg = pl.mt == 1 ? 4 : 3;       // D: blocks in flight per wave
+  pl.kchunk = p.k / 128;
+  return pl;
 }
 
-template bool launch_gemm_4bit_wk<bf16_t>(int, int, int, const bf16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                          const float*, bf16_t*, int);
-template bool launch_gemm_4bit_wk<fp16_t>(int, int, int, const fp16_t*, int, const uint8_t*, int, SkStats, int, int,
-                                          const float*, fp16_t*, int);
+template <typename T>
+void wk_launch(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  const SkStats st = ft_stats<SkStats>(p, a);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), 0, current_stream(), p.m, p.n, p.k, a.A, p.lda, a.B, p.ldb,
+                       st, a.code, a.out, a.ldc);
+  };
+  const bool mt1 = pl.mt == 1, wide = pl.waves == 4;
+  if (p.nested) {
+    if (mt1) wide ? go(k_gemm_4bit_wk<T, 1, 4, 4, true>) : go(k_gemm_4bit_wk<T, 1, 8, 4, true>);
+    else wide ? go(k_gemm_4bit_wk<T, 2, 4, 3, true>) : go(k_gemm_4bit_wk<T, 2, 8, 3, true>);
+  } else {
+    if (mt1) wide ? go(k_gemm_4bit_wk<T, 1, 4, 4, false>) : go(k_gemm_4bit_wk<T, 1, 8, 4, false>);
+    else wide ? go(k_gemm_4bit_wk<T, 2, 4, 3, false>) : go(k_gemm_4bit_wk<T, 2, 8, 3, false>);
+  }
+}
+template void wk_launch<bf16_t>(const FtProblem&, const FtArgs<bf16_t>&, const FtPlan&);
+template void wk_launch<fp16_t>(const FtProblem&, const FtArgs<fp16_t>&, const FtPlan&);
 
 }  // namespace bnb
 

@@ -169,73 +169,84 @@ k_gemv_4bit_tok(int M, int K, int ntok, const T* __restrict__ A, int lda, const 
 
 constexpr int GT_MAX_TOKENS = 4;
 
-// m = weight rows, ntok = activation rows (2..GT_MAX_TOKENS), k = in features.  False: shape, alignment or size
-// does not fit (the caller then uses the few-token GEMM).
-template <typename T, bool NESTED>
-static bool launch_gemv_tok(int m, int ntok, int k, const T* A, int lda, const uint8_t* B, int ldb, GemvStats st,
-                            const float* datatype, T* out, int ldc) {
-  if (ntok < 2 || ntok > GT_MAX_TOKENS || k > GV_MAX_K) return false;
+// the compiled (R rows per wave, U chunks per lane) instances
+#define GT_INSTANCES(X) X(1, 1) X(1, 2) X(1, 3) X(1, 4) X(1, 6) X(1, 8) X(2, 1) X(2, 2) X(2, 3) X(2, 4) X(3, 1) X(3, 2) X(4, 1) X(4, 2)
+static bool gt_instance(int R, int U) {
+#define GT_IS(r, u) if (R == r && U == u) return true;
+  GT_INSTANCES(GT_IS)
+#undef GT_IS
+  return false;
+}
+
+// m = weight rows, n = activation rows (2..GT_MAX_TOKENS), k = in features.  FT_NONE: shape, alignment or size does not
+// fit (the few-token GEMM runs it then).
+FtPlan gemv_tok_plan(const FtProblem& p) {
+  FtPlan pl;
+  const int m = p.m, ntok = p.n, k = p.k;
+  if (k % 32 || !ft_aligned(p) || p.blocksize < 32 || !ft_pow2(p.blocksize) || (p.nested && !ft_pow2(p.blocksize2)))
+    return pl;
+  if (ntok < 2 || ntok > GT_MAX_TOKENS || k > GV_MAX_K) return pl;
   // fewer weight rows than CUs leave most of the chip idle here (whole rows per workgroup): the split-K few-token
   // kernel is faster there (128 x 8192 at 4 rows 12.8 -> 9.0 us; profiles/lab/r02_gemv_wide.txt)
-  if (m < device_cu_count()) return false;
+  if (m < device_cu_count()) return pl;
   const int tok = ntok <= 2 ? 2 : 4;
-  const size_t lds = GT_TABLE_BYTES + (size_t)tok * 2 * k + (NESTED ? 1024 : 0);
-  if (lds > 160 * 1024) return false;
+  const size_t lds = GT_TABLE_BYTES + (size_t)tok * 2 * k + (p.nested ? 1024 : 0);
+  if (lds > 160 * 1024) return pl;
   const bool two = lds <= GT_TWO_PER_CU_LDS;
   int U = ((k >> 5) + 63) / 64;
   if (U > 4) U = U <= 6 ? 6 : 8;
   const int max_waves = two ? 8 : 16;
-  const int r_max = min(4, (tok == 4 ? 6 : 8) / U);                 // R x U loads per lane (R 4 x U 2 at 4 tokens spills)
-  if (r_max < 1) return false;
+  const int r_max = min(4, (tok == 4 ? 6 : 8) / max(U, 1));          // R x U loads per lane (R 4 x U 2 at 4 tokens spills)
+  if (r_max < 1) return pl;
   // two (or one) balanced workgroups per CU; more when that many rows per wave would not fit the registers
   int G = (two ? 2 : 1) * device_cu_count();
   if ((long long)G * max_waves * r_max < m) G = (int)((m + (long long)max_waves * r_max - 1) / ((long long)max_waves * r_max));
   G = min(G, m);
   const int rows = (m + G - 1) / G;
   const int R = (rows + max_waves - 1) / max_waves;
-  if (R > r_max) return false;
-  const int nw = (rows + R - 1) / R;
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(G), dim3(64 * nw), lds, current_stream(), m, k, ntok, A, lda, B, st, datatype, out,
-                       ldb, ldc, G);
-    return true;
-  };
-#define GT_CASES(TK)                                                                     \
-  switch (R * 8 + U) {                                                                   \
-    case 8 + 1: return go(k_gemv_4bit_tok<T, 1, 1, NESTED, TK>);                         \
-    case 8 + 2: return go(k_gemv_4bit_tok<T, 1, 2, NESTED, TK>);                         \
-    case 8 + 3: return go(k_gemv_4bit_tok<T, 1, 3, NESTED, TK>);                         \
-    case 8 + 4: return go(k_gemv_4bit_tok<T, 1, 4, NESTED, TK>);                         \
-    case 8 + 6: return go(k_gemv_4bit_tok<T, 1, 6, NESTED, TK>);                         \
-    case 8 + 8: return go(k_gemv_4bit_tok<T, 1, 8, NESTED, TK>);                         \
-    case 16 + 1: return go(k_gemv_4bit_tok<T, 2, 1, NESTED, TK>);                        \
-    case 16 + 2: return go(k_gemv_4bit_tok<T, 2, 2, NESTED, TK>);                        \
-    case 16 + 3: return go(k_gemv_4bit_tok<T, 2, 3, NESTED, TK>);                        \
-    case 16 + 4: return go(k_gemv_4bit_tok<T, 2, 4, NESTED, TK>);                        \
-    case 24 + 1: return go(k_gemv_4bit_tok<T, 3, 1, NESTED, TK>);                        \
-    case 24 + 2: return go(k_gemv_4bit_tok<T, 3, 2, NESTED, TK>);                        \
-    case 32 + 1: return go(k_gemv_4bit_tok<T, 4, 1, NESTED, TK>);                        \
-    case 32 + 2: return go(k_gemv_4bit_tok<T, 4, 2, NESTED, TK>);                        \
-    default: return false;                                                               \
-  }
-  if (tok == 2) { GT_CASES(2) }
-  else { GT_CASES(4) }
-#undef GT_CASES
+  if (R > r_max || !gt_instance(R, U)) return pl;
+  pl.kernel = FT_GEMV_TOK;
+  pl.grid = G;
+  pl.waves = (rows + R - 1) / R;
+  pl.threads = 64 * pl.waves;
+  pl.mt = tok;
+  pl.rg = R;
+  pl.cfg = U;
+  pl.lds = (int)lds;
+  pl.kchunk = k >> 5;
+  return pl;
 }
 
+template <typename T, bool NESTED>
+static void gemv_tok_launch_stats(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  const GemvStats st = ft_stats<GemvStats>(p, a);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(pl.threads), (size_t)pl.lds, current_stream(), p.m, p.k, p.n, a.A, p.lda,
+                       a.B, st, a.code, a.out, p.ldb, a.ldc, pl.grid);
+  };
+#define GT_TOK2(r, u) if (pl.rg == r && pl.cfg == u) return go(k_gemv_4bit_tok<T, r, u, NESTED, 2>);
+#define GT_TOK4(r, u) if (pl.rg == r && pl.cfg == u) return go(k_gemv_4bit_tok<T, r, u, NESTED, 4>);
+  if (pl.mt == 2) { GT_INSTANCES(GT_TOK2) }
+  else { GT_INSTANCES(GT_TOK4) }
+#undef GT_TOK2
+#undef GT_TOK4
+}
 template <typename T>
-static int gemv_tokens(int m, int ntok, int k, const T* A, int lda, const uint8_t* B, int ldb, const float* absmax,
-                       const uint8_t* absmax_q, const float* code2, const float* absmax2, const float* offset,
-                       const float* datatype, T* out, int ldc, int blocksize, int blocksize2) {
+void gemv_tok_launch(const FtProblem& p, const FtArgs<T>& a, const FtPlan& pl) {
+  if (p.nested) gemv_tok_launch_stats<T, true>(p, a, pl);
+  else gemv_tok_launch_stats<T, false>(p, a, pl);
+}
+template void gemv_tok_launch<bf16_t>(const FtProblem&, const FtArgs<bf16_t>&, const FtPlan&);
+template void gemv_tok_launch<fp16_t>(const FtProblem&, const FtArgs<fp16_t>&, const FtPlan&);
+
+// the GEMV alone (cgemm_4bit_inference_tokens_*): 0 launched, 1 it does not take the problem, 2 the launch failed
+template <typename T>
+static int gemv_tokens(int m, int ntok, int k, const FtArgs<T>& a, int lda, int ldb, int blocksize, int blocksize2) {
   if (m <= 0) return 0;
-  const bool nested = absmax_q != nullptr;
-  if (k % 32 || ldb % 16 || lda % 8 || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || blocksize < 32 ||
-      (blocksize & (blocksize - 1)) || (nested && (blocksize2 <= 0 || (blocksize2 & (blocksize2 - 1)))))
-    return 1;
-  GemvStats st{absmax, absmax_q, code2, absmax2, offset, __builtin_ctz(blocksize), nested ? __builtin_ctz(blocksize2) : 0};
-  const bool ok = nested ? launch_gemv_tok<T, true>(m, ntok, k, A, lda, B, ldb, st, datatype, out, ldc)
-                         : launch_gemv_tok<T, false>(m, ntok, k, A, lda, B, ldb, st, datatype, out, ldc);
-  if (!ok) return 1;
+  const FtProblem p = ft_problem(m, ntok, k, lda, ldb, blocksize, blocksize2, a, 0, true);
+  const FtPlan pl = gemv_tok_plan(p);
+  if (pl.kernel == FT_NONE) return 1;
+  gemv_tok_launch<T>(p, a, pl);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error((int)e, "gemv_4bit_tokens"); return 2; }
   return 0;
@@ -254,15 +265,15 @@ int cgemm_4bit_inference_tokens_bf16(int m, int ntok, int k, bf16_t* A, int lda,
                                      unsigned char* absmax_q, float* code2, float* absmax2, float* offset,
                                      float* datatype, bf16_t* out, int ldc, int blocksize, int blocksize2) {
   BNB_RANGE("cgemm_4bit_inference_tokens_bf16");
-  return gemv_tokens<bf16_t>(m, ntok, k, A, lda, B, ldb, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc,
-                             blocksize, blocksize2);
+  return gemv_tokens<bf16_t>(m, ntok, k, FtArgs<bf16_t>{A, B, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc, nullptr},
+                             lda, ldb, blocksize, blocksize2);
 }
 int cgemm_4bit_inference_tokens_fp16(int m, int ntok, int k, fp16_t* A, int lda, unsigned char* B, int ldb, float* absmax,
                                      unsigned char* absmax_q, float* code2, float* absmax2, float* offset,
                                      float* datatype, fp16_t* out, int ldc, int blocksize, int blocksize2) {
   BNB_RANGE("cgemm_4bit_inference_tokens_fp16");
-  return gemv_tokens<fp16_t>(m, ntok, k, A, lda, B, ldb, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc,
-                             blocksize, blocksize2);
+  return gemv_tokens<fp16_t>(m, ntok, k, FtArgs<fp16_t>{A, B, absmax, absmax_q, code2, absmax2, offset, datatype, out, ldc, nullptr},
+                             lda, ldb, blocksize, blocksize2);
 }
 
 }  // extern "C"

@@ -39,6 +39,4 @@ struct GemvStats {
   int bs_shift, bs2_shift;
 };
 
-int device_cu_count();   // CUs of the current device (cached; gemv4bit.hip)
-
 }  // namespace bnb

@@ -940,7 +940,6 @@ struct HgKnobs {
 struct HgPlan {
   int wi, wj, splits, kchunk;
 };
-int device_cu_count();   // CUs of the current device (cached; gemv4bit.hip)
 static HgPlan hgemm_plan(const HgKnobs& kn, int m, int n, int k, int elem, bool allow_split, bool full_tiles_only,
                          bool allow_quarter = false) {
   const int nkt = (int)((long long)k * elem / 128);

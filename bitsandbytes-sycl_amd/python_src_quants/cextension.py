@@ -52,8 +52,8 @@ class BNBNativeLibrary:
                      "cgemm_4bit_inference_naive_nested_fp16", "cgemm_4bit_inference_naive_nested_bf16",
                      "cdequantize_blockwise_nested_fp16_fp4", "cdequantize_blockwise_nested_fp16_nf4",
                      "cdequantize_blockwise_nested_bf16_fp4", "cdequantize_blockwise_nested_bf16_nf4",
-                     "cint8_row_quant_fp16", "cgemm_4bit_inference_nested_ws_bf16",
-                     "cgemm_4bit_inference_nested_ws_fp16", "cset_cpu_threads", "cgemm_4bit_fewtok_takes", "chgemm_tn_ws_bf16", "chgemm_tn_ws_fp16",
+                     "cint8_row_quant_fp16", "cgemm_4bit_inference_ws_bf16", "cgemm_4bit_inference_ws_fp16",
+                     "cset_cpu_threads", "chgemm_tn_ws_bf16", "chgemm_tn_ws_fp16",
                      "cipc_handle_size", "cipc_get_handle", "cipc_open_handle", "cipc_close_handle", "callgather_ipc_16",
                      "cprobe_lds_poison", "cprobe_lds_peek", "croctx_enabled",
                      "cigemv_row_dequant_fp16", "cint8_linear_rows_fp16", "cigemv_set_mode", "cigemv_max_rows",

@@ -841,17 +841,13 @@ def _gemm_workspace(device, nbytes: int) -> Optional[Tensor]:
 # tests that size a "large prefill" problem (the static rule no longer needs it).
 GEMM_4BIT_DEQUANT_MIN_ROWS = 2048
 GEMM_4BIT_DEQUANT_MIN_FEATURES = 1024
-# Up to this many activation rows the C side runs the few-token kernels (gemm4bit_fewtok.hip whole-K up to 32 rows,
-# gemm4bit_skinny.hip split-K at 33..64 rows; round 2: 11008 x 4096 at 33..64 rows 43.7 -> 27.3..31.2 us against the
-# library pair, profiles/lab/r02_fewtoken_64rows.txt); with nested statistics the Python side calls its one-launch
-# entry point directly.
+# Up to this many activation rows the few-token kernels run (SK_MAX_TOKENS), the only ones that decode compressed
+# statistics in-kernel; which of them takes a shape is the C side's launch plan (gemm4bit.hip fewtoken_plan, reported
+# by cgemm_4bit_plan; round 2: 11008 x 4096 at 33..64 rows 43.7 -> 27.3..31.2 us against the library pair,
+# profiles/lab/r02_fewtoken_64rows.txt).
 GEMM_4BIT_FEW_TOKENS = 64
-# (round 2's rule for 65..256 rows of wide weights; the round-4 static rule covers those rows with k_hgemm's 128-row
-# tile and split-K -- 11008 x 4096 at 96 / 128 / 256 rows 52.5 / 54.0 / 60.4 us against the library pair's 48.9 / 51.8
-# / 58.7 and the fused kernel's 62.1 / 66.2 / 74.0, profiles/lab/r04_route_sweep.txt)
-GEMM_4BIT_WIDE_MAX_ROWS = 256
-# 2..GEMM_4BIT_GEMV_TOKENS activation rows: where the C side's rule takes the shape (cgemm_4bit_fewtok_takes; round 3,
-# measured faster), the whole-K MFMA few-token kernel (gemm4bit_fewtok.hip); elsewhere the multi-row GEMV
+# 2..GEMM_4BIT_GEMV_TOKENS activation rows: where that plan's rule for the whole-K MFMA few-token kernel
+# (gemm4bit_fewtok.hip) takes the shape (round 3, measured faster) that kernel; elsewhere the multi-row GEMV
 # (gemv4bit_tok.hip: every weight byte looked up once and dotted with each row, whole K per workgroup, one launch,
 # rows bit-identical to gemv_4bit on each row).  Batch invariance is therefore given up by default: on the MFMA kernel
 # a row of a 2..4-row batch is within the GEMV tolerance of gemv_4bit on that row, not bit-identical to it (both are
@@ -862,8 +858,7 @@ GEMM_4BIT_GEMV_TOKENS = 4
 # The GEMM after the dequantise is the hand-written k_hgemm (hgemm.hip, chgemm_tn_*: 4 waves on v_mfma_f32_16x16x32,
 # 256 x 256 tiles -- 128 x 128 per wave -- or the half-width 256 x 128 / 128 x 256 tiles, split-K over the GEMM
 # workspace on small grids; the C side's launch plan, hgemm.hip hgemm_plan / chgemm_tn_plan) on every shape it takes
-# (_hgemm_fits).  HGEMM_MIN_TILES: the 256 x 256 grid size from which no split is considered.
-HGEMM_MIN_TILES = 192
+# (_hgemm_fits).
 
 # Routing is deterministic by default: the static rule above picks the kernel from the shape alone, so every process
 # and every rank runs the same kernels on the same shape and returns the same bits.  BNB_ROUTE_TUNING=1 (or
@@ -1130,22 +1125,9 @@ def _dequant_workspace(device, dtype, numel: int) -> Tensor:
     return ws[:numel]
 
 
-def _fewtok_takes(n: int, rows: int, k: int, blocksize: int) -> bool:
-    """Whether the C side runs the whole-K few-token kernel (gemm4bit_fewtok.hip) for this shape; 2..4 rows then go
-    there instead of the multi-row GEMV (measured faster wherever its rule takes the shape, profiles/lab/r03_fewtok32.txt).
-    Asked on every call (one cheap ctypes call, 2..4-row products only): the C answer applies the same conditions as the
-    launch, including every A/B knob (fewtok mode, the older few-token kernels, the split-K geometry), so no cached
-    answer can go stale when a knob changes."""
-    return bool(lib.cgemm_4bit_fewtok_takes(ct.c_int32(n), ct.c_int32(rows), ct.c_int32(k), ct.c_int32(blocksize)))
-
-
-_FEWTOK_MODE = [0]
-
-
 def set_fewtok_mode(mode: int) -> None:
     """Test / A-B knob of the whole-K few-token kernel: 0 = auto, 1 = off, 2 = wherever it fits."""
     lib.cgemm_4bit_set_fewtok_mode(ct.c_int(mode))
-    _FEWTOK_MODE[0] = mode
 
 
 _EVENT_POOL: list = []
@@ -1165,36 +1147,14 @@ def _stage_events(n: int) -> list:
     return [_EVENT_POOL.pop() if _EVENT_POOL else torch.cuda.Event(enable_timing=True) for _ in range(n)]
 
 
-def _gemm_4bit_tokens(A2: Tensor, Bc: Tensor, state: QuantState, out: Tensor, absmax: Optional[Tensor],
-                      events: Optional[list]) -> bool:
-    """2..GEMM_4BIT_GEMV_TOKENS rows through cgemm_4bit_inference_tokens_* (one launch; compressed statistics
-    decoded in the kernel).  False when the entry point declines the shape (nothing launched)."""
-    N, K = state.shape[0], state.shape[1]
-    rows = A2.shape[0]
-    nested = absmax is None and _nested_stats_in_kernel_ok(state)
-    if nested:
+def _stats_4bit(state: QuantState, absmax: Optional[Tensor], device) -> tuple:
+    """A 4-bit weight's statistics as the C entry points take them: ([absmax, absmax_q, code2, absmax2, offset],
+    blocksize2).  Compressed statistics that a kernel can decode in place (no absmax given) go as they are; otherwise
+    plain fp32 ones, the given absmax or the decoded one."""
+    if absmax is None and _nested_stats_in_kernel_ok(state):
         s2 = state.state2
-        stats = [None, state.absmax, s2.code, s2.absmax, _offset_on(state, A2.device)]
-        bs2 = s2.blocksize
-    else:
-        stats = [absmax if absmax is not None else _absmax_fp32(state), None, None, None, None]
-        bs2 = 0
-    prev_device = pre_call(A2.device)
-    is_on_gpu([A2, Bc, out, state.code] + [t for t in stats if t is not None])
-    ev = _stage_events(2) if events is not None else None
-    if ev:
-        ev[0].record()
-    fn = lib.cgemm_4bit_inference_tokens_bf16 if A2.dtype == torch.bfloat16 else lib.cgemm_4bit_inference_tokens_fp16
-    rc = fn(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(Bc),
-            ct.c_int32((K + 1) // 2), *[get_ptr(t) for t in stats], get_ptr(state.code), get_ptr(out), ct.c_int32(N),
-            ct.c_int32(state.blocksize), ct.c_int32(bs2))
-    post_call(prev_device)
-    if rc == 2:
-        raise RuntimeError(f"bitsandbytes HIP kernel error: {lib.cget_last_error_message().decode()}")
-    if rc == 0 and ev:
-        ev[1].record()
-        events.append(("gemm", ev[0], ev[1]))
-    return rc == 0
+        return [None, state.absmax, s2.code, s2.absmax, _offset_on(state, device)], s2.blocksize
+    return [absmax if absmax is not None else _absmax_fp32(state), None, None, None, None], 0
 
 
 # Prefetched weights (gemm_4bit(..., prefetch=...)): per (device, dtype, stream) two weight slots and the slot + identity
@@ -1235,14 +1195,7 @@ def _launch_prefetch_gemm(A2: Tensor, W: Tensor, out: Tensor, ws: Optional[Tenso
     an = pf[2] if len(pf) > 2 else None
     rows, K = A2.shape
     N = W.shape[0]
-    nested = an is None and sn.nested and _nested_stats_in_kernel_ok(sn)
-    if nested:
-        s2 = sn.state2
-        stats = [None, sn.absmax, s2.code, s2.absmax, _offset_on(sn, A2.device)]
-        bs2 = s2.blocksize
-    else:
-        stats = [an if an is not None else _absmax_fp32(sn), None, None, None, None]
-        bs2 = 0
+    stats, bs2 = _stats_4bit(sn, an, A2.device)
     Bc = Bn                      # (contiguous: gemm_4bit drops the hint otherwise)
     is_on_gpu([Bc, target] + [t for t in stats if t is not None])
     fn = lib.chgemm_tn_pf_bf16 if A2.dtype == torch.bfloat16 else lib.chgemm_tn_pf_fp16
@@ -1250,6 +1203,127 @@ def _launch_prefetch_gemm(A2: Tensor, W: Tensor, out: Tensor, ws: Optional[Tenso
               get_ptr(out), ct.c_int32(N), get_ptr(ws), ct.c_longlong(ws_bytes), get_ptr(Bc),
               *[get_ptr(t) for t in stats], ct.c_int32(1 if sn.quant_type == "fp4" else 0), ct.c_int32(sn.blocksize),
               ct.c_int32(bs2), ct.c_longlong(sn.shape[0] * sn.shape[1]), get_ptr(target))
+
+
+def _gemm_4bit_fused(A2: Tensor, Bc: Tensor, state: QuantState, out: Tensor, absmax: Optional[Tensor],
+                     events: Optional[list]) -> None:
+    """The "fused" route: one call of cgemm_4bit_inference_ws_* -- the C side's launch plan picks the kernel (the
+    multi-row GEMV for up to GEMM_4BIT_GEMV_TOKENS rows, the few-token kernels, the tile kernels).  Compressed statistics
+    go in as they are up to GEMM_4BIT_FEW_TOKENS rows (one launch, no decode); where the plan is left with a kernel that
+    needs plain ones (return 1, nothing launched) they are decoded and the call repeated."""
+    N, K = state.shape[0], state.shape[1]
+    rows = A2.shape[0]
+    if absmax is None and rows > GEMM_4BIT_FEW_TOKENS:
+        absmax = _absmax_fp32(state)
+    ws_bytes = int(lib.cgemm_4bit_workspace_bytes(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K)))
+    ws = _gemm_workspace(A2.device, ws_bytes)
+    fn = lib.cgemm_4bit_inference_ws_bf16 if A2.dtype == torch.bfloat16 else lib.cgemm_4bit_inference_ws_fp16
+    ev = _stage_events(2) if events is not None else None
+    while True:
+        stats, bs2 = _stats_4bit(state, absmax, A2.device)
+        prev_device = pre_call(A2.device)
+        is_on_gpu([A2, Bc, out, state.code] + [t for t in stats if t is not None])
+        if ev:
+            ev[0].record()
+        rc = fn(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(Bc),
+                ct.c_int32((K + 1) // 2), *[get_ptr(t) for t in stats], get_ptr(state.code), get_ptr(out), ct.c_int32(N),
+                ct.c_int32(state.blocksize), ct.c_int32(bs2), get_ptr(ws), ct.c_longlong(ws_bytes),
+                ct.c_int32(GEMM_4BIT_GEMV_TOKENS))
+        post_call(prev_device)
+        if rc != 1 or stats[0] is not None:
+            break
+        absmax = _absmax_fp32(state)
+    if rc:
+        raise RuntimeError(f"bitsandbytes HIP 4-bit GEMM returned {rc}: "
+                           f"{lib.cget_last_error_message().decode() if rc == 2 else 'shape not supported'}")
+    if ev:
+        ev[1].record()
+        events.append(("gemm", ev[0], ev[1]))
+
+
+def _gemm_4bit_pair(A2: Tensor, Bc: Tensor, state: QuantState, out: Tensor, absmax: Optional[Tensor],
+                    events: Optional[list], reuse_weight: bool, route: str, prefetch: Optional[tuple]) -> None:
+    """The "hgemm" / "library" / "library_tn" routes: the weight dequantised into a slot (unless a prefetch or a
+    reuse_weight call left it there), then the GEMM named by the route."""
+    N, K = state.shape[0], state.shape[1]
+    rows = A2.shape[0]
+    device, dtype = A2.device, A2.dtype
+    if absmax is None and not state.nested:
+        absmax = _absmax_fp32(state)
+    prev_device = pre_call(device)
+    is_on_gpu([A2, Bc, out, state.code] + ([absmax] if absmax is not None else []))
+    ev = _stage_events(3) if events is not None else None
+    if ev:
+        ev[0].record()
+    key = (device, dtype, _stream_key(device))
+    meta = _weight_meta(Bc, state, absmax)
+    ready = _PF_READY.get(key)
+    cur_slot = None
+    if ready is not None and ready[1] == meta:
+        # dequantised by the previous call's GEMM (prefetch): consumed here (row chunks of this same product that
+        # follow with reuse_weight read it again, until a prefetch overwrites the slot)
+        cur_slot = ready[0]
+        del _PF_READY[key]
+        _PF_CUR[key] = ready
+    elif reuse_weight and _PF_CUR.get(key, (None, None))[1] == meta:
+        cur_slot = _PF_CUR[key][0]
+    if cur_slot is not None:
+        W = _PF_WS[key][cur_slot][:N * K].view(N, K)
+    else:
+        W = _dequant_workspace(device, dtype, N * K).view(N, K)
+    if cur_slot is None and not (reuse_weight and _DEQ_META.get(key) == meta):
+        if absmax is None and not _dequant_4bit_nested(Bc, state, W):   # nested stats decoded in-kernel
+            absmax = _absmax_fp32(state)
+        if absmax is not None:
+            qt = "fp4" if state.quant_type == "fp4" else "nf4"
+            getattr(lib, f"cdequantize_blockwise_{_QB[dtype]}_{qt}")(
+                get_ptr(None), get_ptr(Bc), get_ptr(absmax), get_ptr(W), ct.c_int(state.blocksize),
+                ct.c_int(N * K))
+        _DEQ_META[key] = meta
+        if ev:
+            ev[1].record()
+            events.append(("dequantize", ev[0], ev[1]))
+    elif ev:
+        ev[1].record()
+    if route == "hgemm":
+        # the hand-written GEMM (hgemm.hip); split-K over a workspace on small tile grids (chgemm_tn_ws_*)
+        ws_bytes = int(lib.chgemm_tn_workspace_bytes(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K)))
+        ws = _gemm_workspace(device, ws_bytes)
+        rc = 1
+        if prefetch is not None:
+            sn = prefetch[1]
+            nn = sn.shape[0] * sn.shape[1]
+            # (if the slots are re-made larger here, W still holds the old slot this call reads; both new ones
+            # are free)
+            slots = _pf_slots(key, device, dtype, max(nn, N * K))
+            target = 1 - cur_slot if cur_slot is not None else 0
+            rc = _launch_prefetch_gemm(A2, W, out, ws, ws_bytes, prefetch, slots[target][:nn])
+            if rc == 0:
+                if _PF_CUR.get(key, (None,))[0] == target:
+                    _PF_CUR.pop(key, None)
+                _PF_READY[key] = (target, _weight_meta(prefetch[0], sn, prefetch[2] if len(prefetch) > 2 else None))
+        if rc == 1:
+            fn = lib.chgemm_tn_ws_bf16 if dtype == torch.bfloat16 else lib.chgemm_tn_ws_fp16
+            rc = fn(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(W),
+                    ct.c_int32(K), get_ptr(out), ct.c_int32(N), get_ptr(ws), ct.c_longlong(ws_bytes))
+        post_call(prev_device)
+        if rc:
+            raise RuntimeError(f"bitsandbytes HIP GEMM (chgemm_tn) returned {rc}: "
+                               f"{lib.cget_last_error_message().decode() if rc == 2 else 'shape not supported'}")
+    elif route == "library_tn":
+        # the library GEMM with the per-shape solution search (gemm_lib.hip, rocBLAS)
+        fn = lib.cgemm_tn_bf16 if dtype == torch.bfloat16 else lib.cgemm_tn_fp16
+        rc = fn(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(W),
+                ct.c_int32(K), get_ptr(out), ct.c_int32(N))
+        post_call(prev_device)
+        if rc:
+            raise RuntimeError(f"bitsandbytes HIP library GEMM error: {lib.cget_last_error_message().decode()}")
+    else:
+        post_call(prev_device)
+        torch.matmul(A2, W.t(), out=out.view(rows, N))
+    if ev:
+        ev[2].record()
+        events.append(("gemm", ev[1], ev[2]))
 
 
 def gemm_4bit(A: Tensor, B: Tensor, state: QuantState, out: Optional[Tensor] = None,
@@ -1297,7 +1371,9 @@ def gemm_4bit(A: Tensor, B: Tensor, state: QuantState, out: Optional[Tensor] = N
         measured = gemm_4bit_measured_route(A2, state, absmax)   # a table handed over by import_routes / the plan file
         if measured is not None:
             route = measured
-    if route == "hgemm" and not _hgemm_fits(rows, N, K):
+    if route == "fused":
+        _gemm_4bit_fused(A2, Bc, state, out, absmax, events)
+    elif route == "hgemm" and not _hgemm_fits(rows, N, K):
         # beyond one launch's 32-bit offsets: the same pair in row / weight chunks (also where a measured / imported
         # route, which covers a quarter-octave of row counts, names "hgemm" near the limit).  reuse_weight and prefetch
         # do not apply there (each call dequantises its weight chunk by chunk); events get one "gemm" pair around it all
@@ -1308,124 +1384,8 @@ def gemm_4bit(A: Tensor, B: Tensor, state: QuantState, out: Optional[Tensor] = N
         if ev:
             ev[1].record()
             events.append(("gemm", ev[0], ev[1]))
-        return out.view(*A.shape[:-1], N)
-    library = route in ("library", "library_tn", "hgemm")
-    if (not library and 2 <= rows <= GEMM_4BIT_GEMV_TOKENS and not _fewtok_takes(N, rows, K, state.blocksize)
-            and _gemm_4bit_tokens(A2, Bc, state, out, absmax, events)):
-        return out.view(*A.shape[:-1], N)
-    if (absmax is None and not library and rows <= GEMM_4BIT_FEW_TOKENS and _nested_stats_in_kernel_ok(state)):
-        # few tokens, compressed statistics: one launch of the weight-streaming kernel that decodes the
-        # nested absmax in-kernel (no separate decode launch)
-        ws_bytes = int(lib.cgemm_4bit_workspace_bytes(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K)))
-        ws = _gemm_workspace(A.device, ws_bytes)
-        s2 = state.state2
-        offset = _offset_on(state, A.device)
-        prev_device = pre_call(A.device)
-        is_on_gpu([A2, Bc, out, state.absmax, s2.code, s2.absmax, offset, state.code])
-        ev = _stage_events(2) if events is not None else None
-        if ev:
-            ev[0].record()
-        fn = (lib.cgemm_4bit_inference_nested_ws_bf16 if A.dtype == torch.bfloat16
-              else lib.cgemm_4bit_inference_nested_ws_fp16)
-        rc = fn(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K), get_ptr(A2), get_ptr(Bc), get_ptr(state.absmax),
-                get_ptr(s2.code), get_ptr(s2.absmax), get_ptr(offset), get_ptr(state.code), get_ptr(out),
-                ct.c_int32(K), ct.c_int32((K + 1) // 2), ct.c_int32(N), ct.c_int32(state.blocksize),
-                ct.c_int32(s2.blocksize), get_ptr(ws), ct.c_longlong(ws_bytes))
-        if rc == 0:
-            post_call(prev_device)
-            if ev:
-                ev[1].record()
-                events.append(("gemm", ev[0], ev[1]))
-            return out.view(*A.shape[:-1], N)
-        post_call(prev_device)
-    if absmax is None and not (library and state.nested):
-        absmax = _absmax_fp32(state)
-    prev_device = pre_call(A.device)
-    is_on_gpu([A2, Bc, out, state.code] + ([absmax] if absmax is not None else []))
-    ev = _stage_events(3) if events is not None else None
-    if ev:
-        ev[0].record()
-    if library:
-        key = (A.device, A.dtype, _stream_key(A.device))
-        meta = _weight_meta(Bc, state, absmax)
-        ready = _PF_READY.get(key)
-        cur_slot = None
-        if ready is not None and ready[1] == meta:
-            # dequantised by the previous call's GEMM (prefetch): consumed here (row chunks of this same product that
-            # follow with reuse_weight read it again, until a prefetch overwrites the slot)
-            cur_slot = ready[0]
-            del _PF_READY[key]
-            _PF_CUR[key] = ready
-        elif reuse_weight and _PF_CUR.get(key, (None, None))[1] == meta:
-            cur_slot = _PF_CUR[key][0]
-        if cur_slot is not None:
-            W = _PF_WS[key][cur_slot][:N * K].view(N, K)
-        else:
-            W = _dequant_workspace(A.device, A.dtype, N * K).view(N, K)
-        if cur_slot is None and not (reuse_weight and _DEQ_META.get(key) == meta):
-            if absmax is None and not _dequant_4bit_nested(Bc, state, W):   # nested stats decoded in-kernel
-                absmax = _absmax_fp32(state)
-            if absmax is not None:
-                qt = "fp4" if state.quant_type == "fp4" else "nf4"
-                getattr(lib, f"cdequantize_blockwise_{_QB[A.dtype]}_{qt}")(
-                    get_ptr(None), get_ptr(Bc), get_ptr(absmax), get_ptr(W), ct.c_int(state.blocksize),
-                    ct.c_int(N * K))
-            _DEQ_META[key] = meta
-            if ev:
-                ev[1].record()
-                events.append(("dequantize", ev[0], ev[1]))
-        elif ev:
-            ev[1].record()
-        if route == "hgemm":
-            # the hand-written GEMM (hgemm.hip); split-K over a workspace on small tile grids (chgemm_tn_ws_*)
-            ws_bytes = int(lib.chgemm_tn_workspace_bytes(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K)))
-            ws = _gemm_workspace(A.device, ws_bytes)
-            rc = 1
-            if prefetch is not None:
-                sn = prefetch[1]
-                nn = sn.shape[0] * sn.shape[1]
-                # (if the slots are re-made larger here, W still holds the old slot this call reads; both new ones
-                # are free)
-                slots = _pf_slots(key, A.device, A.dtype, max(nn, N * K))
-                target = 1 - cur_slot if cur_slot is not None else 0
-                rc = _launch_prefetch_gemm(A2, W, out, ws, ws_bytes, prefetch, slots[target][:nn])
-                if rc == 0:
-                    if _PF_CUR.get(key, (None,))[0] == target:
-                        _PF_CUR.pop(key, None)
-                    _PF_READY[key] = (target, _weight_meta(prefetch[0], sn, prefetch[2] if len(prefetch) > 2 else None))
-            if rc == 1:
-                fn = lib.chgemm_tn_ws_bf16 if A.dtype == torch.bfloat16 else lib.chgemm_tn_ws_fp16
-                rc = fn(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(W),
-                        ct.c_int32(K), get_ptr(out), ct.c_int32(N), get_ptr(ws), ct.c_longlong(ws_bytes))
-            post_call(prev_device)
-            if rc:
-                raise RuntimeError(f"bitsandbytes HIP GEMM (chgemm_tn) returned {rc}: "
-                                   f"{lib.cget_last_error_message().decode() if rc == 2 else 'shape not supported'}")
-        elif route == "library_tn":
-            # the library GEMM with the per-shape solution search (gemm_lib.hip, rocBLAS)
-            fn = lib.cgemm_tn_bf16 if A.dtype == torch.bfloat16 else lib.cgemm_tn_fp16
-            rc = fn(ct.c_int32(rows), ct.c_int32(N), ct.c_int32(K), get_ptr(A2), ct.c_int32(K), get_ptr(W),
-                    ct.c_int32(K), get_ptr(out), ct.c_int32(N))
-            post_call(prev_device)
-            if rc:
-                raise RuntimeError(f"bitsandbytes HIP library GEMM error: {lib.cget_last_error_message().decode()}")
-        else:
-            post_call(prev_device)
-            torch.matmul(A2, W.t(), out=out.view(rows, N))
-        if ev:
-            ev[2].record()
-            events.append(("gemm", ev[1], ev[2]))
-        return out.view(*A.shape[:-1], N)
-    ws_bytes = int(lib.cgemm_4bit_workspace_bytes(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K)))
-    ws = _gemm_workspace(A.device, ws_bytes)
-    fn = lib.cgemm_4bit_inference_code_ws_bf16 if A.dtype == torch.bfloat16 else lib.cgemm_4bit_inference_code_ws_fp16
-    fn(ct.c_int32(N), ct.c_int32(rows), ct.c_int32(K), get_ptr(A2), get_ptr(Bc), get_ptr(absmax),
-       get_ptr(state.code), get_ptr(out), ct.c_int32(K), ct.c_int32((K + 1) // 2), ct.c_int32(N),
-       ct.c_int32(state.blocksize), get_ptr(ws), ct.c_longlong(ws_bytes))
-    post_call(prev_device)
-    if ev:
-        ev[2].record()
-        events.append(("gemm", ev[0], ev[2]))
+    else:
+        _gemm_4bit_pair(A2, Bc, state, out, absmax, events, reuse_weight, route, prefetch)
     return out.view(*A.shape[:-1], N)
 
 

@@ -101,9 +101,6 @@ void cgemm_4bit_set_fewtoken_kernel(int which);
 /* [additive, testing] the whole-K few-token kernel (gemm4bit_fewtok.hip; 1..32 activation rows, LDS-DMA weight ring,
  * 16x16x32 MFMA, tried before the kernels above): 0 = auto (where its shape rule takes it), 1 = off, 2 = wherever it fits */
 void cgemm_4bit_set_fewtok_mode(int mode);
-/* [additive] 1 when the 4-bit GEMM entry points (cgemm_4bit_inference*, the few-token ws / nested entries) run that
- * kernel for m out features, n activation rows, k in features and this blocksize, else 0 */
-int cgemm_4bit_fewtok_takes(int m, int n, int k, int blocksize);
 
 /* [additive, testing] GEMV kernel choice: 0 = auto (the balanced-range kernel where the shape fits, else the
  * 4-waves-x-R-rows kernel), 1 = the 4-waves-x-R-rows kernel only; both give identical bits */
@@ -128,26 +125,28 @@ void cgemm_4bit_inference_code_fp16(int m, int n, int k, bnb_fp16* A, unsigned c
                                     bnb_fp16* out, int lda, int ldb, int ldc, int blocksize);
 void cgemm_4bit_inference_code_bf16(int m, int n, int k, bnb_bf16* A, unsigned char* B, float* absmax, float* datatype,
                                     bnb_bf16* out, int lda, int ldb, int ldc, int blocksize);
-/* [additive] the same with a caller-owned fp32 workspace that lets small tile grids (narrow column
- * shards, few tokens) run split-K; size it with cgemm_4bit_workspace_bytes (0 = split-K not used for this
- * shape).  A NULL or smaller workspace falls back to the unsplit kernels. */
-void cgemm_4bit_inference_code_ws_fp16(int m, int n, int k, bnb_fp16* A, unsigned char* B, float* absmax,
-                                       float* datatype, bnb_fp16* out, int lda, int ldb, int ldc, int blocksize,
-                                       float* workspace, long long workspace_bytes);
-void cgemm_4bit_inference_code_ws_bf16(int m, int n, int k, bnb_bf16* A, unsigned char* B, float* absmax,
-                                       float* datatype, bnb_bf16* out, int lda, int ldb, int ldc, int blocksize,
-                                       float* workspace, long long workspace_bytes);
+/* [additive] the same product for the Python layer, with a caller-owned fp32 workspace for the kernels that split K
+ * (size it with cgemm_4bit_workspace_bytes; a NULL or smaller workspace leaves the unsplit kernels) and the statistics
+ * either plain (absmax fp32, absmax_q = NULL) or compressed (absmax = NULL; absmax_q uint8 codes, code2 256-entry map,
+ * absmax2 per blocksize2 codes, offset: one fp32 on the device), decoded in-kernel by the few-token kernels (ntok <= 64;
+ * replaces the absmax decode launch + GEMM of the M > 1 path, ref:functional.py:1346-1350 + autograd/_functions.py:507).
+ * One launch plan (gemm_common.hpp, fewtoken_plan) picks the kernel; this is the only entry that may run 2..4 rows on
+ * the multi-row GEMV of cgemm_4bit_inference_tokens_*, for up to gemv_rows rows (0: never).  Returns 0 when launched, 1 when only a kernel that needs plain
+ * statistics is left (nothing launched: decode the statistics and call again), 2 on error. */
+int cgemm_4bit_inference_ws_fp16(int m, int ntok, int k, bnb_fp16* A, int lda, unsigned char* B, int ldb, float* absmax,
+                                 unsigned char* absmax_q, float* code2, float* absmax2, float* offset, float* datatype,
+                                 bnb_fp16* out, int ldc, int blocksize, int blocksize2, float* workspace,
+                                 long long workspace_bytes, int gemv_rows);
+int cgemm_4bit_inference_ws_bf16(int m, int ntok, int k, bnb_bf16* A, int lda, unsigned char* B, int ldb, float* absmax,
+                                 unsigned char* absmax_q, float* code2, float* absmax2, float* offset, float* datatype,
+                                 bnb_bf16* out, int ldc, int blocksize, int blocksize2, float* workspace,
+                                 long long workspace_bytes, int gemv_rows);
+/* [additive, testing] the launch plan of cgemm_4bit_inference_ws_* for contiguous, aligned operands and a full
+ * workspace: out[0..15] = {kernel (FtKernel in csrc/gemm_common.hpp), workgroups, threads per workgroup, K splits,
+ * k-chunk, MT / TOK, RG / NB / R / D, waves, S4, X8, cfg / U, dynamic LDS bytes, 1 if a reduce launch follows, workspace
+ * bytes used (low, high 32 bits), 0} */
+void cgemm_4bit_plan(int m, int ntok, int k, int blocksize, int blocksize2, int nested, int* out);
 long long cgemm_4bit_workspace_bytes(int m, int n, int k);
-/* [additive] few tokens (n <= 64, k % 128 == 0): the weight-streaming kernel with compressed statistics
- * (absmax_q uint8 codes, code2 256-entry map, absmax2 per blocksize2 codes, offset: one fp32 on the
- * device) decoded in-kernel -- replaces the absmax decode launch + GEMM of the M > 1 path
- * (ref:functional.py:1346-1350 + autograd/_functions.py:507).  The plain-absmax calls above use the
- * same kernel for n <= 64 when the workspace fits.  Returns 0 when launched, 1 when the shape,
- * alignment or workspace does not fit (the caller then decodes absmax and uses the _ws entry points). */
-int cgemm_4bit_inference_nested_ws_fp16(int m, int n, int k, bnb_fp16* A, unsigned char* B, unsigned char* absmax_q,
-                                        float* code2, float* absmax2, float* offset, float* datatype, bnb_fp16* out,
-                                        int lda, int ldb, int ldc, int blocksize, int blocksize2, float* workspace,
-                                        long long workspace_bytes);
 /* [additive] 4-bit weight x 2..4 activation rows in one launch (gemv4bit_tok.hip; replaces the M > 1 pair
  * dequantize_4bit + F.linear, ref:autograd/_functions.py:491-507, for batched decode): out[t * ldc + r], t < ntok.
  * Statistics plain (absmax fp32, absmax_q = NULL) or compressed (absmax = NULL; absmax_q, code2, absmax2, offset,
@@ -161,10 +160,6 @@ int cgemm_4bit_inference_tokens_fp16(int m, int ntok, int k, bnb_fp16* A, int ld
                                      float* absmax, unsigned char* absmax_q, float* code2, float* absmax2,
                                      float* offset, float* datatype, bnb_fp16* out, int ldc, int blocksize,
                                      int blocksize2);
-int cgemm_4bit_inference_nested_ws_bf16(int m, int n, int k, bnb_bf16* A, unsigned char* B, unsigned char* absmax_q,
-                                        float* code2, float* absmax2, float* offset, float* datatype, bnb_bf16* out,
-                                        int lda, int ldb, int ldc, int blocksize, int blocksize2, float* workspace,
-                                        long long workspace_bytes);
 /* [additive, testing] force the GEMM tile kernel: 0 = auto, 128 = 128x128, 256 = 256x256 */
 void cgemm_4bit_set_tile(int tile);
 

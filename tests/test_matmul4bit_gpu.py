@@ -503,11 +503,11 @@ def test_gemm_4bit_few_tokens_entry_point_declines(dev):
     out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
     s2 = st.state2
     off = st.offset.reshape(1).float()
-    rc = F.lib.cgemm_4bit_inference_nested_ws_bf16(
-        ct.c_int32(N), ct.c_int32(M), ct.c_int32(K), F.get_ptr(X), F.get_ptr(q), F.get_ptr(st.absmax),
-        F.get_ptr(s2.code), F.get_ptr(s2.absmax), F.get_ptr(off), F.get_ptr(st.code), F.get_ptr(out),
-        ct.c_int32(K), ct.c_int32(K // 2), ct.c_int32(N), ct.c_int32(64), ct.c_int32(s2.blocksize), None,
-        ct.c_longlong(0))
+    rc = F.lib.cgemm_4bit_inference_ws_bf16(
+        ct.c_int32(N), ct.c_int32(M), ct.c_int32(K), F.get_ptr(X), ct.c_int32(K), F.get_ptr(q), ct.c_int32(K // 2),
+        None, F.get_ptr(st.absmax), F.get_ptr(s2.code), F.get_ptr(s2.absmax), F.get_ptr(off), F.get_ptr(st.code),
+        F.get_ptr(out), ct.c_int32(N), ct.c_int32(64), ct.c_int32(s2.blocksize), None, ct.c_longlong(0),
+        ct.c_int32(F.GEMM_4BIT_GEMV_TOKENS))
     assert rc == 1
     Y = F.gemm_4bit(X, q, st)                  # routed to the tile kernels
     Wd = F.dequantize_4bit(q, st)
@@ -911,8 +911,8 @@ def test_fewtok32_kernel_vs_oracle(dev, dtype, nested, qt, bs, mnk):
 @pytest.mark.parametrize("rows", [2, 3, 4])
 @pytest.mark.parametrize("shape", [(11008, 4096), (4096, 4096), (4096, 11008)])
 def test_fewtok_default_rows_close_to_gemv_and_deterministic(dev, nested, rows, shape):
-    """The DEFAULT route of 2..4 activation rows (round 3: the whole-K MFMA few-token kernel wherever
-    cgemm_4bit_fewtok_takes says so, else the multi-row GEMV): each row within the GEMV tolerance of gemv_4bit on that
+    """The DEFAULT route of 2..4 activation rows (round 3: the whole-K MFMA few-token kernel wherever the launch plan's
+    rule for it takes the shape -- cgemm_4bit_plan --, else the multi-row GEMV): each row within the GEMV tolerance of gemv_4bit on that
     row alone (|d| <= 2e-2 * rms + 2e-2 * |ref|; bit-identity is given up on the MFMA kernel), and the same bits on a
     second call (deterministic)."""
     F = _F()
