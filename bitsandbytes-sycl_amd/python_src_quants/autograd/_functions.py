@@ -7,8 +7,11 @@ The forward passes are built around this backend's kernels rather than the refer
 * int8 -- an inference forward (no outliers, no gradient) quantises the activations in ONE pass
   (F.int8_row_quant, rows only) and runs the fused igemmlt + mm_dequant kernel on the row-major int8 weight
   (F.igemmlt_dequant); the training / outlier forward keeps the reference's double_quant (rows and columns, plus the
-  COO outliers above the threshold) and adds the fp16 outlier product.  A weight that only exists in a
+  COO outliers above the threshold) and adds the fp16 outlier product; a training forward whose weight is frozen and
+  has no threshold quantises rows only as well.  A weight that only exists in a
   col_turing / col_ampere layout (a legacy checkpoint's CxB) goes through transform + igemmlt + mm_dequant.
+  The input gradient of a stored row-major weight is functional.int8_linear_dgrad (transposing int8 dequantise +
+  k_hgemm where its route rule takes it); the gradient is quantised only for the weight gradient.
 * 4-bit -- functional.gemm_4bit for any number of rows (its own routing: multi-row GEMV, few-token kernel, fused
   kernel, or dequantise + the hand-written k_hgemm), replacing dequantize_4bit + F.linear (reference line 507); a
   single activation row without gradient takes the decode GEMV exactly as the reference routes it.
@@ -81,14 +84,19 @@ def _empty_backward(ctx):
 
 
 # ----------------------------------------------------------------------------- LLM.int8 pieces
-def _quantize_activations(A2: torch.Tensor, state: MatmulLtState, for_backward: bool):
-    """(CA, CAt, SCA, SCAt, coo) of the fp16 activations.  Without outliers or backward only the row half is needed,
-    and the one-pass kernel produces it; otherwise double_quant (rows, columns and the COO outliers)."""
+def _quantize_activations(A2: torch.Tensor, state: MatmulLtState, need_columns: bool):
+    """(CA, CAt, SCA, SCAt, coo) of the fp16 activations.  The column half (CAt, SCAt) is read by the weight gradient
+    alone: without outliers and without it only the row half is needed, and the one-pass kernel produces it (the bits
+    of double_quant's row half); otherwise double_quant (rows, columns and the COO outliers), whose column half is
+    dropped when nothing will read it."""
     A16 = A2.to(torch.float16)
-    if state.threshold == 0.0 and not for_backward:
+    if state.threshold == 0.0 and not need_columns:
         CA, SCA = F.int8_row_quant(A16)
         return CA, None, SCA, None, None
-    return F.double_quant(A16, threshold=state.threshold)
+    CA, CAt, SCA, SCAt, coo = F.double_quant(A16, threshold=state.threshold)
+    if not need_columns:
+        CAt = SCAt = None
+    return CA, CAt, SCA, SCAt, coo
 
 
 def _quantize_weight(B: torch.Tensor, state: MatmulLtState) -> torch.Tensor:
@@ -222,7 +230,8 @@ class MatMul8bitLt(torch.autograd.Function):
             output = F.int8_linear_outliers(A2.to(torch.float16), state.CB, state.SCB, bias=bias,
                                             threshold=state.threshold).to(A2.dtype)
         else:
-            CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, for_backward)
+            # the column half of the quantised activations feeds grad_B only: a frozen weight does not ask for it
+            CA, CAt, SCA, SCAt, coo = _quantize_activations(A2, state, bool(ctx.needs_input_grad[1]))
             if state.has_fp16_weights:
                 B = _quantize_weight(B, state)
             subA = _split_outliers(A2, B, CA, CAt, coo, state)
@@ -255,14 +264,19 @@ class MatMul8bitLt(torch.autograd.Function):
         state = ctx.state
         grad_bias = grad_output.sum(0, dtype=ctx.dtype_bias) if need_bias else None
         g2 = grad_output.reshape(-1, grad_output.shape[-1]).contiguous() if grad_output.dim() == 3 else grad_output
-        Cg, Cgt, SCg, SCgt, _ = F.double_quant(g2.to(torch.float16))
         grad_B = grad_A = None
         if need_B:
             # grad_W[o, i] = sum_t g[t, o] A[t, i]: the int8 product over the token dimension, column-normalised
+            _, Cgt, _, SCgt, _ = F.double_quant(g2.to(torch.float16))
             grad_B = F.igemmlt_dequant(Cgt.t().contiguous(), CAt.t().contiguous(), SCgt, SCAt)
             if state.threshold > 0.0 and subA is not None:
                 grad_B[:, idx] += torch.matmul(g2.t(), subA)
-        if need_A:
+        if need_A and state.CB is not None:
+            # grad @ W on the stored row-major weight: the transposing int8 dequantise into the weight workspace +
+            # k_hgemm where functional.int8_linear_dgrad's route rule takes it (it makes the gradient contiguous
+            # there), the dequantised weight + torch.matmul as before elsewhere
+            grad_A = F.int8_linear_dgrad(g2.to(ctx.dtype_A), state.CB, state.SCB).view(ctx.grad_shape)
+        elif need_A:
             W = _dequantized_weight(state, ctx.dtype_A)
             grad_A = torch.matmul(g2.to(ctx.dtype_A), W).view(ctx.grad_shape).to(ctx.dtype_A)
         return grad_A, grad_B, None, grad_bias, None

@@ -82,6 +82,10 @@ class BNBNativeLibrary:
                 fn.restype, fn.argtypes = ct.c_int, [ct.c_void_p] * 3 + [ct.c_int] * 4
                 fn = getattr(lib, f"cdequantize_blockwise_nested_t_{t}_{q}")
                 fn.restype, fn.argtypes = ct.c_int, [ct.c_void_p] * 6 + [ct.c_int] * 5
+        # the transposing int8 row dequantise (dequant_int8_t.hip): (CB, SCB, out, rows, cols, ldo)
+        for name in ("cdequantize_int8_rows_t_bf16", "cdequantize_int8_rows_t_fp16"):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = ct.c_int, [ct.c_void_p] * 3 + [ct.c_int] * 3
 
     def __getattr__(self, item):
         fn = getattr(self._lib, item)

@@ -2294,6 +2294,157 @@ def int8_row_quant(A: Tensor, out_row: Optional[Tensor] = None) -> Tuple[Tensor,
     return out_row, row_stats
 
 
+def _int8_weight_16(CB: Tensor, SCB: Tensor, dtype) -> Tensor:
+    """W ~ CB * SCB / 127 in `dtype`, [N, K]: the expression MatMul8bitLt.backward dequantises a stored CB with
+    (autograd._functions._dequantized_weight) -- the row scale SCB * fp32(1 / 127) first, one fp32 product, one
+    rounding."""
+    return CB.to(dtype, copy=True).mul_(SCB.unsqueeze(1).mul(1.0 / 127.0))
+
+
+def _dequant_int8_t_launch(CB: Tensor, SCB: Tensor, out: Tensor) -> int:
+    """cdequantize_int8_rows_t_*: the contiguous int8 [N, K] weight and its fp32 row absmax into out[k, n] (out: [K, N]
+    bf16/fp16 rows of stride out.stride(0), unit column stride).  Returns the C code: 0 launched, 1 not supported
+    (nothing launched); a launch error raises."""
+    N, K = CB.shape
+    prev_device = pre_call(CB.device)
+    is_on_gpu([CB, SCB, out])
+    fn = lib.cdequantize_int8_rows_t_bf16 if out.dtype == torch.bfloat16 else lib.cdequantize_int8_rows_t_fp16
+    rc = fn(CB.data_ptr(), SCB.data_ptr(), out.data_ptr(), N, K, out.stride(0))
+    post_call(prev_device)
+    if rc == 2:
+        raise RuntimeError(f"bitsandbytes HIP kernel error: {lib.cget_last_error_message().decode()}")
+    return rc
+
+
+def dequantize_int8_t(CB: Tensor, SCB: Tensor, dtype, out: Optional[Tensor] = None) -> Tensor:
+    """The transposed dequantisation of an LLM.int8 weight: CB (int8 [N, K]) with its row absmax SCB ([N]) -> a [K, N]
+    tensor with the bits of CB.to(dtype).mul_(SCB.unsqueeze(1).mul(1.0 / 127.0)).t().contiguous(), in out's dtype
+    (`dtype` without out).  bf16 / fp16 with N % 8 == 0 and K % 16 == 0 run the transposing kernel
+    (dequant_int8_t.hip: no [N, K] intermediate); `out` may be a [K, N] window of a wider buffer (unit column stride,
+    row stride % 8 == 0, 16-B aligned).  Every other case (fp32, other shapes or strides) dequantises untransposed and
+    copies the transpose, so the function is total."""
+    if CB.device.type != "cuda":
+        raise NotImplementedError(f"Device type not supported for int8 dequantization: {CB.device.type}")
+    if CB.dim() != 2 or CB.dtype != torch.int8:
+        raise ValueError(f"dequantize_int8_t takes a 2-D int8 weight, got {CB.dtype} of shape {tuple(CB.shape)}")
+    N, K = CB.shape
+    if SCB.numel() != N:
+        raise ValueError(f"dequantize_int8_t: SCB must hold {N} row statistics, got {SCB.numel()}")
+    if out is None:
+        out = torch.empty((K, N), dtype=dtype, device=CB.device)
+    elif tuple(out.shape) != (K, N):
+        raise ValueError(f"dequantize_int8_t: out must be [{K}, {N}], got {tuple(out.shape)}")
+    if N == 0 or K == 0:
+        return out
+    if out.dtype in (torch.float16, torch.bfloat16) and out.stride(1) == 1:
+        CBc = CB if CB.is_contiguous() else CB.contiguous()
+        S = SCB.reshape(-1)
+        if S.dtype != torch.float32 or not S.is_contiguous():
+            S = S.float().contiguous()
+        if _dequant_int8_t_launch(CBc, S, out) == 0:
+            return out
+    out.copy_(_int8_weight_16(CB, SCB.reshape(-1), out.dtype).t())
+    return out
+
+
+# The input gradient of a frozen LLM.int8 layer, grad[..., N] @ W[N, K] with W ~ CB * SCB / 127
+# (MatMul8bitLt.backward; LoRA on an int8 base model: once per frozen projection per step).  As gemm_4bit_dgrad: the
+# weight is dequantised already transposed (dequantize_int8_t, W^T [K, N]) into the weight workspace and the product
+# is the chgemm_tn_* call m = rows, n = K, k = N -- no [N, K] allocation per backward, no vendor GEMM.
+# Measured (tools/int8_dgrad_probe.py, profiles/lab/int8_dgrad_probe.txt; Llama-2-7B weights, bf16, graph replay):
+# "hgemm" is ahead of the previous expression at 4096 / 256 / 16 rows on [4096, 4096] (0.67 / 0.50 / 0.44 of its time),
+# [11008, 4096] (0.67 / 0.33 / 0.28) and [4096, 11008] (0.58 / 0.36 / 0.33), each by far more than either arm's spread
+# (at most 10 %) -- the previous expression's dequantise alone (48 / 110 / 110 us) costs more than the whole "hgemm"
+# call at 16 and 256 rows.  So no row or shape constant: the wide product at few rows, which the 4-bit gradient leaves
+# on the library pair (GEMM_4BIT_DGRAD_WIDE_MAX_ROWS), is ahead here as well.
+INT8_DGRAD_ROUTES = ("hgemm", "library")
+
+
+def int8_linear_dgrad_shape_ok(rows: int, N: int, K: int) -> bool:
+    """The shapes the "hgemm" route of int8_linear_dgrad takes: the contraction N in whole 64-wide k-tiles of k_hgemm,
+    K % 16 == 0 for the transposing dequantise, one launch's 32-bit offsets (_hgemm_fits with n = K, k = N; the
+    dequantise's 2 GiB of output).  There is no chunked form."""
+    return N % 64 == 0 and K % 16 == 0 and _hgemm_fits(rows, K, N) and K * N < 2 ** 31
+
+
+def int8_linear_dgrad_supported(G: Tensor, CB: Optional[Tensor], SCB: Optional[Tensor]) -> bool:
+    """Whether int8_linear_dgrad can run G @ W on the project's kernels: a bf16 / fp16 gradient [..., N] against a
+    contiguous int8 CB [N, K] with N fp32 row statistics, and a shape that passes int8_linear_dgrad_shape_ok."""
+    if CB is None or SCB is None or G.dtype not in (torch.bfloat16, torch.float16) or G.dim() < 1:
+        return False
+    if CB.dtype != torch.int8 or CB.dim() != 2 or not CB.is_contiguous() or CB.data_ptr() % 16:
+        return False
+    N, K = CB.shape
+    if SCB.dtype != torch.float32 or SCB.numel() != N or not SCB.is_contiguous() or G.shape[-1] != N:
+        return False
+    rows = G.numel() // N if N else 0
+    return int8_linear_dgrad_shape_ok(rows, N, K)
+
+
+def int8_linear_dgrad_static_route(rows: int, N: int, K: int, dtype=torch.bfloat16) -> str:
+    """The deterministic route of the int8 input gradient: "hgemm" (dequantize_int8_t + k_hgemm) wherever the shape
+    rule holds for a 16-bit gradient (measured ahead on every probed shape, see above), else "library" (the 16-bit
+    dequantised weight + torch.matmul)."""
+    if dtype in (torch.bfloat16, torch.float16) and int8_linear_dgrad_shape_ok(rows, N, K):
+        return "hgemm"
+    return "library"
+
+
+def int8_linear_dgrad(G: Tensor, CB: Tensor, SCB: Tensor, out: Optional[Tensor] = None,
+                      _route: Optional[str] = None) -> Tensor:
+    """G[..., N] @ W[N, K] -> [..., K] with W ~ CB * SCB / 127 rounded once into G's dtype: the input gradient of the
+    LLM.int8 out = A @ W^T.  Route "hgemm": the weight dequantised transposed into the weight workspace
+    (dequantize_int8_t), then k_hgemm (chgemm_tn_ws_*, split-K over the GEMM workspace on small grids); the workspace
+    then holds W^T, so a later gemm_4bit(..., reuse_weight=True) dequantises again.  Route "library": the expression
+    MatMul8bitLt.backward used before, torch.matmul(G, CB.to(dtype).mul_(SCB / 127)) -- the route outside
+    int8_linear_dgrad_supported (fp32 gradients, other shapes or strides, no rows) and wherever
+    int8_linear_dgrad_static_route says so.  _route forces one (internal)."""
+    if G.device.type != "cuda":
+        raise NotImplementedError(f"Device type not supported for the int8 input gradient: {G.device.type}")
+    N, K = CB.shape
+    supported = int8_linear_dgrad_supported(G, CB, SCB)
+    rows = G.numel() // N if N else 0
+    route = int8_linear_dgrad_static_route(rows, N, K, G.dtype) if supported else "library"
+    if _route is not None:
+        if _route not in INT8_DGRAD_ROUTES:
+            raise ValueError(f"int8_linear_dgrad: unknown route {_route!r}")
+        if _route == "hgemm" and not supported:
+            raise ValueError("int8_linear_dgrad: route 'hgemm' needs a bf16/fp16 gradient, a contiguous int8 CB with "
+                             "fp32 row statistics, out_features % 64 == 0, in_features % 16 == 0 and one launch's "
+                             "32-bit offsets")
+        route = _route
+    if route == "library" or rows == 0:
+        res = torch.matmul(G, _int8_weight_16(CB, SCB, G.dtype))
+        if out is None:
+            return res
+        out.view(res.shape).copy_(res)
+        return out.view(res.shape)
+    G2 = G.reshape(-1, N)
+    if not G2.is_contiguous() or G2.data_ptr() % 16:
+        G2 = G2.contiguous()
+    if out is None:
+        out = torch.empty((rows, K), dtype=G.dtype, device=G.device)
+    key = (G.device, G.dtype, _stream_key(G.device))
+    Wt = _dequant_workspace(G.device, G.dtype, K * N).view(K, N)
+    # the workspace stops holding a forward-orientation 4-bit weight here: reuse_weight must not trust it
+    _DEQ_META.pop(key, None)
+    if _dequant_int8_t_launch(CB, SCB, Wt) != 0:
+        raise RuntimeError("bitsandbytes HIP transposing int8 dequantise declined a shape "
+                           "int8_linear_dgrad_supported accepts")
+    ws_bytes = int(lib.chgemm_tn_workspace_bytes(ct.c_int32(rows), ct.c_int32(K), ct.c_int32(N)))
+    ws = _gemm_workspace(G.device, ws_bytes)
+    prev_device = pre_call(G.device)
+    is_on_gpu([G2, Wt, out])
+    fn = lib.chgemm_tn_ws_bf16 if G.dtype == torch.bfloat16 else lib.chgemm_tn_ws_fp16
+    rc = fn(ct.c_int32(rows), ct.c_int32(K), ct.c_int32(N), get_ptr(G2), ct.c_int32(N), get_ptr(Wt), ct.c_int32(N),
+            get_ptr(out), ct.c_int32(K), get_ptr(ws), ct.c_longlong(ws_bytes))
+    post_call(prev_device)
+    if rc:
+        raise RuntimeError(f"bitsandbytes HIP GEMM (chgemm_tn) returned {rc}: "
+                           f"{lib.cget_last_error_message().decode() if rc == 2 else 'shape not supported'}")
+    return out.view(*G.shape[:-1], K)
+
+
 def extract_outliers(A, SA, idx):
     """Gather int8 columns `idx` of a turing/ampere-tiled matrix (ref:functional.py:2914-2936)."""
     shapeA, formatA = SA[0], SA[1]

@@ -483,6 +483,17 @@ int cdequantize_blockwise_nested_t_fp16_nf4(unsigned char* A, unsigned char* abs
         float* offset, bnb_fp16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
 int cdequantize_blockwise_nested_t_fp16_fp4(unsigned char* A, unsigned char* absmax_q, float* code2, float* absmax2,
         float* offset, bnb_fp16* out, int blocksize, int blocksize2, int rows, int cols, int ldo);
+/* [additive] transposing int8 row dequantise (dequant_int8_t.hip): the LLM.int8 weight CB (int8, row-major
+ * [rows = N, cols = K]) with its row absmax SCB (fp32 [N]) goes to out[k * ldo + n] =
+ * float(CB[n, k]) * s, s = SCB[n] * (float)(1.0 / 127.0) in fp32 -- bf16: the fp32 product, then one RNE cast; fp16:
+ * the exact product rounded once (one fused multiply-convert, a -0 product stored as +0) -- which are the bits of
+ * torch's CB.to(T).mul_(SCB.unsqueeze(1).mul(1.0 / 127.0)).t().contiguous() on gfx950: the W^T [K, N] operand of the
+ * input-gradient product grad @ W through chgemm_tn_* (m = gradient rows, n = K, k = N).  Needs rows % 8 == 0, cols % 16 == 0,
+ * ldo >= rows, ldo % 8 == 0, 16-B aligned CB and out, rows * cols and every output byte offset below 2 GiB.  Returns 0
+ * when launched (or nothing to do), 1 when the shape / alignment is not supported (nothing launched), 2 on a launch
+ * error (cget_last_error). */
+int cdequantize_int8_rows_t_bf16(const signed char* CB, const float* SCB, bnb_bf16* out, int rows, int cols, int ldo);
+int cdequantize_int8_rows_t_fp16(const signed char* CB, const float* SCB, bnb_fp16* out, int rows, int cols, int ldo);
 /* fp32 states: ref:sycl/pythonInterface.cpp:223-241 (reference suffixes; bf16 siblings additive).
  * max_unorm > 0 (adam, momentum, rmsprop) clips the norm of the update against max_unorm * param_norm: `unorm` then
  * points to one float, which the call overwrites with the squared L2 norm of this step's trial update (a fixed-order
