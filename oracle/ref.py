@@ -31,13 +31,30 @@ NF4_PY_TABLE = [-1.0, -0.6961928009986877, -0.5250730514526367, -0.3949174880981
                 0.33791524171829224, 0.44070982933044434, 0.5626170039176941,
                 0.7229568362236023, 1.0]
 
+
+def f32_literal(text: str) -> np.float32:
+    """The value a C++ compiler gives the literal `<text>f`: the decimal rounded ONCE to fp32.
+
+    np.float32(float(text)) rounds twice (decimal -> double -> float).  The NF4 thresholds are midpoints of two
+    fp32 values, 25-bit numbers that sit (to the 16 printed digits) on a tie between two floats: the double lands on
+    the tie and round-to-even then picks a float that the single rounding of the printed decimal does not.  Four of
+    the 15 differ by one ulp (-0.848..., 0.1202..., 0.5016..., 0.8614...), and an input on such a float takes the
+    other code (kernel_quant.cpp:713, 718, 729, 752)."""
+    from fractions import Fraction
+    d = F32(float(text))
+    exact = Fraction(text)
+    return min((np.nextafter(d, F32(-np.inf)), d, np.nextafter(d, F32(np.inf))),
+               key=lambda v: abs(Fraction(float(v)) - exact))
+
+
 # NF4 quantisation thresholds (float literals of the decision tree), ascending,
 # ref:sycl/sycl_code/kernel_quant.cpp:705-756.  index = #{t : x > t}.
-NF4_THRESHOLDS = np.array(
-    [-0.8480964004993439, -0.6106329262256622, -0.4599952697753906, -0.33967943489551544,
-     -0.23460740596055984, -0.13791173323988914, -0.045525018125772476, 0.03979014977812767,
-     0.1202552504837513, 0.2035212516784668, 0.2920137718319893, 0.3893125355243683,
-     0.5016634166240692, 0.6427869200706482, 0.8614784181118011], dtype=F32)
+NF4_THRESHOLD_LITERALS = (
+    "-0.8480964004993439", "-0.6106329262256622", "-0.4599952697753906", "-0.33967943489551544",
+    "-0.23460740596055984", "-0.13791173323988914", "-0.045525018125772476", "0.03979014977812767",
+    "0.1202552504837513", "0.2035212516784668", "0.2920137718319893", "0.3893125355243683",
+    "0.5016634166240692", "0.6427869200706482", "0.8614784181118011")
+NF4_THRESHOLDS = np.array([f32_literal(t) for t in NF4_THRESHOLD_LITERALS], dtype=F32)
 
 # FP4 quantiser tree, ref:sycl/sycl_code/kernel_quant.cpp:547-594.  Restated as a
 # count over the sorted magnitude thresholds followed by a count->code map:

@@ -32,6 +32,30 @@ def test_nf4_quantize_table_roundtrip_and_ties():
     assert ref.quantize_nf4(np.array([np.nan], F32))[0] == 0
 
 
+def test_threshold_literals_are_rounded_once():
+    """kernel_quant.cpp:705-756 and 547-594 compare with `...f` literals: the compiler rounds the decimal once to
+    fp32.  Through a double (np.float32(float(text))) four NF4 thresholds land one ulp off -- each is the midpoint of
+    two fp32 values, a tie the double hits exactly -- at lines 752, 729, 718 and 713.  The bits below are the
+    single rounding; the GPU agrees on every one (tests/test_quant_boundary_gpu.py, R3)."""
+    th = ref.NF4_THRESHOLDS
+    assert th.dtype == F32 and th.view(np.uint32).tolist() == [
+        3210288345, 3206304368, 3203105920, 3199068790, 3195026668, 3188537532, 3174725745, 1025702655,
+        1039550563, 1045456864, 1049985748, 1053250553, 1056992515, 1059360175, 1063029209]
+    twice = np.array([float(t) for t in ref.NF4_THRESHOLD_LITERALS], F32)
+    assert np.flatnonzero(th != twice).tolist() == [0, 8, 12, 14]
+    assert np.all(np.abs(th.view(np.int32).astype(np.int64) - twice.view(np.int32)) <= 1)
+    from fractions import Fraction
+    for lit, t, tw in zip(ref.NF4_THRESHOLD_LITERALS, th, twice):
+        assert abs(Fraction(float(t)) - Fraction(lit)) <= abs(Fraction(float(tw)) - Fraction(lit))
+    # the FP4 literals are far from any tie: both roundings agree
+    fp4 = ("0.00260417", "0.0859375", "0.20833333", "0.29166667", "0.4166667", "0.583333", "0.8333333")
+    assert np.array_equal(np.array([ref.f32_literal(t) for t in fp4], F32), ref.FP4_MAG_THRESHOLDS)
+    fp4_mag = ("0.00000000", "5.208333333e-03", "0.66666667", "1.00000000", "0.33333333", "0.50000000", "0.16666667",
+               "0.25000000")
+    assert np.array_equal(np.array([ref.f32_literal(t) for t in fp4_mag], F32), ref.FP4_TREE_MAG)
+    assert ref.f32_literal("6.200012e-05") == ref.MM_DEQUANT_CONST
+
+
 def test_fp4_tree_matches_python_table():
     # dDequantizeFP4Tree values (kernel_quant.cpp:520-545) == get_4bit_type('fp4') / 12 (functional.py:1063)
     t = ref.fp4_table()
