@@ -96,6 +96,37 @@ def create_dynamic_map(signed=True, max_exponent_bits=7, total_bits=8):
     return Tensor(data)
 
 
+def create_fp8_map(signed=True, exponent_bits=5, precision_bits=2, total_bits=8):
+    """The 2**total_bits values of a small float format as a sorted 256-entry map scaled to a maximum of 1
+    (ref:functional.py:296-336).  As there, the exponent field counts downwards: field 0 holds the subnormals
+    m / 2**p * 2**-bias, field e >= 1 the normals (1 + m / 2**p) * 2**(bias + 1 - e), with bias = 2**(e_bits - 1).
+    Formats narrower than 8 bits are padded with zeros in the middle of the map."""
+    has_sign = 1 if signed else 0
+    assert exponent_bits + precision_bits == total_bits - has_sign
+    bias = 2 ** (exponent_bits - 1)
+    values = []
+    for field in range(2**exponent_bits):
+        for m in range(2**precision_bits):
+            frac = m / 2**precision_bits
+            value = frac * 2.0**-bias if field == 0 else (1 + frac) * 2.0 ** (bias + 1 - field)
+            values.append(value)
+            if signed:
+                values.append(-value)              # -0.0 follows +0.0 and stays behind it in the stable sort
+    assert len(values) == 2**total_bits
+    code = torch.tensor(sorted(values + [0] * (256 - len(values))), dtype=torch.float32)
+    code /= code.max()
+    return code
+
+
+def create_quantile_map(A, total_bits=8):
+    """A map from the data: the 2**total_bits - 1 estimated quantiles of A plus an exact zero, zero-padded to 256
+    entries, sorted and scaled to a largest magnitude of 1 (ref:functional.py:394-407)."""
+    q = estimate_quantiles(A, num_quantiles=2**total_bits - 1).tolist()
+    q += [0] * (256 - len(q))                      # one zero is a map entry, the rest is padding
+    q = Tensor(sorted(q))
+    return q / q.abs().max()
+
+
 def get_4bit_type(typename, device=None, blocksize=64):
     """16-entry 4-bit code tables, ref:functional.py:1020-1099."""
     if device is None:
@@ -469,6 +500,50 @@ def dequantize_no_absmax(A: Tensor, code: Tensor, out: Optional[Tensor] = None) 
     Ac = A.contiguous()
     lib.cdequantize(get_ptr(code), get_ptr(Ac), get_ptr(out), ct.c_int(A.numel()))
     post_call(prev_device)
+    return out
+
+
+_QUANTILE_SUFFIX = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
+
+
+def estimate_quantiles(A: Tensor, out: Optional[Tensor] = None, offset: float = 1 / 512, num_quantiles=256) -> Tensor:
+    """256 equidistant quantiles of A's empirical distribution, the SRAM-quantiles estimate
+    (ref:functional.py:559-622 -> cestimate_quantiles_<T>).
+
+    A is cut into blocks of 4096 values (fewer than 4096 values are one block; otherwise the ``numel % 4096``
+    trailing values are not used); each block is sorted and read at the 256 positions
+    ``round((offset + t * (1 - 2 * offset) / 255) * (block size - 1))``; the result is the mean over the blocks.
+    ``offset`` trims that fraction of the distribution from each end (the extreme quantiles have the largest
+    estimation error); the default 1/512 is the minimum-entropy choice.  The sort is by IEEE totalOrder and the
+    mean a fixed-order fp64 sum rounded once, so equal inputs give equal bits on every run.  With
+    ``num_quantiles < 256`` the default offset becomes ``1 / (2 * num_quantiles)`` and the 256 values are
+    sub-sampled at ``linspace(0, 255, num_quantiles).long()``.  fp32, fp16 and bf16 GPU tensors of at least 256
+    elements; returns fp32."""
+    if A.numel() < 256:
+        raise NotImplementedError(
+            f"Quantile estimation needs at least 256 values in the Tensor, but Tensor had only {A.numel()} values.")
+    if num_quantiles > 256:
+        raise NotImplementedError(
+            "Currently only a maximum of 256 equally spaced quantiles are supported, but the argument "
+            f"num_quantiles={num_quantiles}")
+    if A.dtype not in _QUANTILE_SUFFIX:
+        raise NotImplementedError(f"Not supported data type {A.dtype}")
+    if A.numel() > 2**31 - 1:
+        raise ValueError(f"estimate_quantiles takes at most 2**31 - 1 values, got {A.numel()}")
+    if num_quantiles < 256 and offset == 1 / 512:
+        offset = 1 / (2 * num_quantiles)           # the default follows the number of quantiles
+    if out is None:
+        out = torch.empty(256, dtype=torch.float32, device=A.device)
+    elif (out.dtype != torch.float32 or out.numel() != 256 or out.device != A.device or not out.is_contiguous()):
+        raise ValueError("estimate_quantiles: out must be a contiguous fp32 tensor of 256 elements on A's device")
+    is_on_gpu([A, out])
+    prev_device = pre_call(A.device)
+    Ac = A.contiguous()
+    getattr(lib, "cestimate_quantiles_" + _QUANTILE_SUFFIX[A.dtype])(
+        get_ptr(Ac), get_ptr(out), ct.c_float(offset), ct.c_int(A.numel()))
+    post_call(prev_device)
+    if num_quantiles < 256:
+        out = out[torch.linspace(0, 255, num_quantiles).long().to(A.device)]
     return out
 
 
@@ -2597,3 +2672,26 @@ def percentile_clipping(grad: Tensor, gnorm_vec: Tensor, step: int, percentile: 
     if current_gnorm > clip_value:
         gnorm_scale = clip_value / current_gnorm
     return current_gnorm, clip_value, gnorm_scale
+
+
+def histogram_scatter_add_2d(histogram: Tensor, index1: Tensor, index2: Tensor, source: Tensor):
+    """histogram[index1[i], index2[i]] += source[i] for every i, in place
+    (ref:functional.py:1859-1874 -> chistogram_scatter_add_2d).
+
+    The flat address is ``index1[i] * histogram.shape[0] + index2[i]``, as in the reference, which is the element
+    [index1[i], index2[i]] of a square histogram only.  The adds are fp32 atomics: exact when every bin's partial
+    sums are representable in fp32 in any order (integer-valued sources with totals below 2**24, counts), otherwise
+    the last bits depend on the order in which the adds arrive.  The indices are not checked."""
+    assert len(histogram.shape) == 2
+    assert histogram.dtype == torch.float32
+    assert source.dtype == torch.float32
+    assert index1.dtype == torch.int32
+    assert index2.dtype == torch.int32
+    assert index1.numel() == index2.numel() == source.numel()
+    assert histogram.is_contiguous()
+    is_on_gpu([histogram, index1, index2, source])
+    prev_device = pre_call(histogram.device)
+    i1, i2, src = index1.contiguous(), index2.contiguous(), source.contiguous()
+    lib.chistogram_scatter_add_2d(get_ptr(histogram), get_ptr(i1), get_ptr(i2), get_ptr(src),
+                                  ct.c_int32(histogram.shape[0]), ct.c_int32(i1.numel()))
+    post_call(prev_device)

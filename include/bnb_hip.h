@@ -60,6 +60,22 @@ void cdequantize_blockwise_bf16_nf4(float* code, unsigned char* A, float* absmax
 void cquantize(float* code, float* A, unsigned char* out, int n);
 void cdequantize(float* code, unsigned char* A, float* out, int n);
 
+/* ---- quantile code books: ref:sycl/pythonInterface.cpp:194-195 (csrc/quantiles.hip) ----
+ * Overwrites code[0..255] with the mean over A's blocks of 4096 of the block's sorted values at the 256 positions
+ * round((offset + t * (1 - 2 offset) / 255) * (valid - 1)).  n < 4096 is one block of n values; otherwise the
+ * n % 4096 trailing values are not read.  Sorted by IEEE totalOrder, summed in fp64 in a fixed order and rounded once
+ * to fp32: the same input gives the same bits on every run, and code need not be zeroed (the reference's port sums
+ * unsorted values with float atomics).  Needs n >= 1 and offset in [0, 0.5].  The first call on a stream allocates a
+ * 2 MB workspace, so a stream must have made one call before a graph capture contains one. */
+void cestimate_quantiles_fp32(float* A, float* code, float offset, int n);
+void cestimate_quantiles_fp16(bnb_fp16* A, float* code, float offset, int n);
+/* [additive] bf16 sibling */
+void cestimate_quantiles_bf16(bnb_bf16* A, float* code, float offset, int n);
+/* ref:sycl/pythonInterface.cpp:286.  histogram[index1[i] * maxidx1 + index2[i]] += src[i] for i < n with the fp32
+ * global atomic add: exact when every bin's partial sums are representable (e.g. integer-valued src, totals below
+ * 2^24), otherwise dependent on the arrival order, as in the reference.  The indices are the caller's contract. */
+void chistogram_scatter_add_2d(float* histogram, int* index1, int* index2, float* src, int maxidx1, int n);
+
 /* ---- host-pointer CPU-path entry points: ref:sycl/pythonInterface.cpp:419-420 (cpu_ops.cpp semantics:
  * division A/absmax, nearest code with ties to the left, code[0] := -1 in place).  Run on the host cores
  * (csrc/cpu_ops.cpp; no HIP call, so they work without a GPU), synchronous on return. */
